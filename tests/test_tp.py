@@ -195,14 +195,17 @@ def test_bench_tp2_torchrun_cpu():
     """The driver-contract bench entrypoint with --tp 2 runs end to end over
     gloo on CPU (2 ranks, one TP replica) and prints the JSON line."""
     import json as _json
+    import os
     import subprocess
     import sys
 
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
            "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29753", "bench.py", "--gpus", "2", "--tp", "2",
            "--steps", "2", "--warmup", "1"]
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=420)
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=420,
+                         cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
     d = _json.loads(line)
