@@ -53,6 +53,10 @@ void sutro_grouped_gemm(void*, const void*, const void*, const int*,
                         int, hipStream_t);
 void sutro_moe_combine(void*, const void*, const long*, const float*, int,
                        int, int, hipStream_t);
+void sutro_logit_penalties(void*, int, const int*, const int*, const int*,
+                           const int*, const int*, const float*, const float*,
+                           const float*, const int*, const float*, int, int,
+                           long, int, int, int, int, int, hipStream_t);
 }
 
 void rmsnorm(torch::Tensor out, torch::Tensor x, torch::Tensor w, double eps) {
@@ -301,6 +305,77 @@ void sampler_fused(torch::Tensor logits, torch::Tensor temps,
                       cur_stream());
 }
 
+// In-place sparse penalties on the rows listed in row_idx (unique rows; one
+// workgroup each). max_hist_len is the host's upper bound on hist_len and
+// sizes the LDS table; the kernel clamps device-side lengths to what the
+// chosen table holds, so a stale bound can drop history but never overflow.
+void logit_penalties(torch::Tensor logits, torch::Tensor row_idx,
+                     torch::Tensor hist, torch::Tensor slot,
+                     torch::Tensor hist_len, torch::Tensor prompt_len,
+                     torch::Tensor rep, torch::Tensor pres, torch::Tensor freq,
+                     c10::optional<torch::Tensor> bias_tok,
+                     c10::optional<torch::Tensor> bias_val, long vl,
+                     long max_hist_len) {
+  CHECK_CUDA(logits); CHECK_CONTIG(logits);
+  const bool f32 = logits.scalar_type() == at::kFloat;
+  TORCH_CHECK(f32 || logits.scalar_type() == at::kBFloat16,
+              "logits must be bf16 or f32");
+  TORCH_CHECK(logits.dim() == 2, "logits must be [n, V]");
+  const long n = logits.size(0), v_row = logits.size(1);
+  TORCH_CHECK(vl >= 0 && vl <= v_row, "vocab_limit exceeds logits row");
+  TORCH_CHECK(v_row < (1L << 31) && n < (1L << 31), "logits too large");
+  const long m = row_idx.numel();
+  if (m == 0) return;
+  auto chk_i32 = [&](const torch::Tensor& t, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.is_contiguous()
+                && t.scalar_type() == at::kInt && t.numel() == m,
+                name, " must be a contiguous int32 GPU tensor of ", m);
+  };
+  auto chk_f32 = [&](const torch::Tensor& t, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.is_contiguous()
+                && t.scalar_type() == at::kFloat && t.numel() == m,
+                name, " must be a contiguous f32 GPU tensor of ", m);
+  };
+  chk_i32(row_idx, "row_idx"); chk_i32(slot, "slot");
+  chk_i32(hist_len, "hist_len"); chk_i32(prompt_len, "prompt_len");
+  chk_f32(rep, "rep"); chk_f32(pres, "pres"); chk_f32(freq, "freq");
+  CHECK_CUDA(hist); CHECK_CONTIG(hist);
+  TORCH_CHECK(hist.scalar_type() == at::kInt && hist.dim() == 2,
+              "hist must be int32 [S, Lcap]");
+  const long n_slots = hist.size(0), lcap = hist.size(1);
+  TORCH_CHECK(lcap < (1L << 31) && n_slots < (1L << 31), "hist too large");
+  long n_bias = 0;
+  const int* btp = nullptr;
+  const float* bvp = nullptr;
+  TORCH_CHECK(bias_tok.has_value() == bias_val.has_value(),
+              "bias_tok and bias_val go together");
+  if (bias_tok.has_value() && bias_tok->numel() > 0) {
+    auto& bt = bias_tok.value();
+    auto& bv = bias_val.value();
+    CHECK_CUDA(bt); CHECK_CONTIG(bt); CHECK_CUDA(bv); CHECK_CONTIG(bv);
+    TORCH_CHECK(bt.scalar_type() == at::kInt && bv.scalar_type() == at::kFloat,
+                "bias_tok int32 / bias_val f32");
+    TORCH_CHECK(bt.dim() == 2 && bt.size(0) == m && bv.dim() == 2
+                && bv.size(0) == m && bv.size(1) == bt.size(1),
+                "bias_tok/bias_val must be [m, B]");
+    n_bias = bt.size(1);
+    TORCH_CHECK(n_bias <= 512, "at most 512 bias entries per row");
+    btp = bt.data_ptr<int>();
+    bvp = bv.data_ptr<float>();
+  }
+  TORCH_CHECK(max_hist_len >= 0 && max_hist_len + n_bias <= 8192,
+              "hist_len + bias entries above 8192: use the torch reference");
+  const long need = 2 * (max_hist_len + n_bias);
+  const int log2_cap = need <= 2048 ? 11 : (need <= 8192 ? 13 : 14);
+  sutro_logit_penalties(logits.data_ptr(), f32 ? 1 : 0,
+                        row_idx.data_ptr<int>(), hist.data_ptr<int>(),
+                        slot.data_ptr<int>(), hist_len.data_ptr<int>(),
+                        prompt_len.data_ptr<int>(), rep.data_ptr<float>(),
+                        pres.data_ptr<float>(), freq.data_ptr<float>(), btp,
+                        bvp, (int)m, (int)n, v_row, (int)vl, (int)n_slots,
+                        (int)lcap, (int)n_bias, log2_cap, cur_stream());
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsnorm", &rmsnorm, "RMSNorm (bf16, CDNA4)");
   m.def("fused_add_rmsnorm", &fused_add_rmsnorm, "residual+=x; x=rmsnorm");
@@ -317,6 +392,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "dropless MoE grouped GEMM (padded segments, static grid)");
   m.def("sampler_fused", &sampler_fused,
         "fused mask+temp+topk/topp+sample+logprob (radix descent, no sort)");
+  m.def("logit_penalties", &logit_penalties,
+        "sparse repetition/presence/frequency penalties + logit_bias "
+        "(LDS hash of the row history, in place)");
   m.def("gemm_tn", &gemm_tn, "bf16 TN GEMM (MFMA, glds dbuf)",
         py::arg("x"), py::arg("w"), py::arg("res") = c10::nullopt,
         py::arg("bm") = 256, py::arg("bn") = 256, py::arg("swz") = 2,

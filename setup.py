@@ -23,6 +23,7 @@ SOURCES = [
     "csrc/gemm_tn.hip",
     "csrc/sampler.hip",
     "csrc/grouped_gemm.hip",
+    "csrc/logit_penalties.hip",
 ]
 
 setup(

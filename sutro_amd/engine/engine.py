@@ -9,7 +9,8 @@ With `EngineConfig.async_decode`, pure-decode steps run one-step-lagged: the
 sampled-token tensor of step N feeds step N+1's input ids directly (no host
 round-trip or device sync on the critical path) and the host applies step
 N's tokens while N+1 executes. Rows that finish decode one extra discarded
-token; FSM-guided rows and mixed prefill steps take the synchronous path.
+token; FSM-guided rows, penalised rows (repetition/presence/frequency
+penalty or logit_bias) and mixed prefill steps take the synchronous path.
 Sync-equivalence is proven by tests (seeded rows, incl. under preemption).
 """
 
@@ -27,6 +28,7 @@ from .batch import ForwardBatch, ScheduledBatch
 from .config import EngineConfig
 from .guided import GuidedFSM
 from .kv_cache import PagedKVCache
+from .penalties import PenaltyState
 from .request import FinishReason, Request, SamplingParams
 from .sampler import Sampler
 from .scheduler import Scheduler
@@ -120,8 +122,14 @@ class LLMEngine:
         # block 0 is reserved scratch: hipGraph padding rows read/write it
         self.scratch_block = self.kv.allocator.allocate(1)[0]
         self.scheduler = Scheduler(cfg, self.kv)
+        # penalised rows keep their token history on the device; the pool is
+        # allocated on first use and a slot follows the row's KV residency
+        self.penalties = PenaltyState(cfg.max_num_seqs, cfg.max_model_len,
+                                      cfg.device)
+        self.scheduler.on_release = self.penalties.release
         self.sampler = Sampler(cfg.device, seed=cfg.seed,
-                               vocab_limit=self.tokenizer.vocab_size)
+                               vocab_limit=self.tokenizer.vocab_size,
+                               penalties=self.penalties)
 
         # size the shared MoE workspace BEFORE any hipGraph capture: big
         # transients allocated inside a capture become graph-owned per
@@ -331,6 +339,10 @@ class LLMEngine:
             return False
         if any(r.fsm_id is not None for r in sub.reqs):
             return False  # the FSM mask needs the sampled token NOW
+        if any(r.sampling.penalised for r in sub.reqs):
+            # same reason: the next step's logit penalties need this step's
+            # token in the row's history, and hist_len is the host total_len
+            return False
         p = self._pending_decode
         if p is None:
             return True

@@ -2,9 +2,13 @@
 
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass, field
 from enum import Enum
 from typing import Any, Dict, List, Optional
+
+
+MAX_LOGIT_BIAS = 512  # entries per request (one LDS-resident list per row)
 
 
 @dataclass
@@ -17,6 +21,13 @@ class SamplingParams:
     stop_token_ids: Optional[List[int]] = None
     stop: Optional[List[str]] = None  # stop strings (trimmed from the output)
     logprobs: bool = True     # accumulate cumulative logprob of sampled tokens
+    # logit adjustments applied before the FSM mask / temperature / top-k/p
+    # (vLLM/OpenAI convention: repetition covers prompt + output, presence
+    # and frequency cover output only; see ops.apply_logit_penalties)
+    repetition_penalty: float = 1.0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    logit_bias: Optional[Dict[int, float]] = None
 
     @classmethod
     def from_dict(cls, d: Optional[Dict[str, Any]], default_max_tokens: int = 256) -> "SamplingParams":
@@ -31,7 +42,63 @@ class SamplingParams:
         sp = cls(**kwargs)
         if "max_tokens" not in d:
             sp.max_tokens = default_max_tokens
+        sp.validate_penalties()
         return sp
+
+    def validate_penalties(self) -> None:
+        """Range-check (and normalize) the penalty fields; ValueError on a
+        bad value. JSON object keys arrive as strings, so logit_bias keys are
+        converted to int here."""
+
+        def _num(name: str, v: Any) -> float:
+            if isinstance(v, bool) or not isinstance(v, (int, float)):
+                raise ValueError(f"{name} must be a number, got {v!r}")
+            v = float(v)
+            if not math.isfinite(v):
+                raise ValueError(f"{name} must be finite, got {v!r}")
+            return v
+
+        rep = _num("repetition_penalty", self.repetition_penalty)
+        if rep <= 0.0:
+            raise ValueError(f"repetition_penalty must be > 0, got {rep!r}")
+        self.repetition_penalty = rep
+        for name in ("presence_penalty", "frequency_penalty"):
+            v = _num(name, getattr(self, name))
+            if not -2.0 <= v <= 2.0:
+                raise ValueError(f"{name} must lie in [-2, 2], got {v!r}")
+            setattr(self, name, v)
+        if self.logit_bias is None:
+            return
+        if not isinstance(self.logit_bias, dict):
+            raise ValueError("logit_bias must be an object of token id -> bias")
+        if len(self.logit_bias) > MAX_LOGIT_BIAS:
+            raise ValueError(
+                f"logit_bias has {len(self.logit_bias)} entries "
+                f"(max {MAX_LOGIT_BIAS})")
+        bias: Dict[int, float] = {}
+        for k, v in self.logit_bias.items():
+            if isinstance(k, str):
+                try:
+                    k = int(k)
+                except ValueError:
+                    raise ValueError(
+                        f"logit_bias key {k!r} is not a token id") from None
+            if isinstance(k, bool) or not isinstance(k, int) or k < 0:
+                raise ValueError(f"logit_bias key {k!r} is not a token id >= 0")
+            v = _num(f"logit_bias[{k}]", v)
+            if not -100.0 <= v <= 100.0:
+                raise ValueError(
+                    f"logit_bias[{k}] must lie in [-100, 100], got {v!r}")
+            if k in bias:
+                raise ValueError(f"logit_bias lists token {k} twice")
+            bias[k] = v
+        self.logit_bias = bias or None
+
+    @property
+    def penalised(self) -> bool:
+        """True when the row's logits need the penalty pass at all."""
+        return (self.repetition_penalty != 1.0 or self.presence_penalty != 0.0
+                or self.frequency_penalty != 0.0 or bool(self.logit_bias))
 
     @property
     def greedy(self) -> bool:

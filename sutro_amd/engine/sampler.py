@@ -4,9 +4,12 @@ Operates over the FULL model vocab (vocab_limit = the tokenizer's vocab; the
 lm_head GEMM and the sampling pass both run at production scale). Guided rows
 pass bit-packed FSM masks (int32 [n, W], see guided.py) straight through.
 
-Sampling semantics (shared bit-for-bit by the torch reference below and the
-fused CDNA4 kernel in csrc/sampler.hip — the kernel avoids any per-row sort,
-so the semantics are defined sort-free):
+Sampling semantics (shared by the torch reference below and the fused CDNA4
+kernel in csrc/sampler.hip — the kernel avoids any per-row sort, so the
+semantics are defined sort-free. The two are semantically equal, not
+bit-identical: the kernel's fixed-point mass sums and the reference's f32
+cumsum can resolve a tie sitting exactly on a top-p / inverse-CDF boundary
+differently. The kernel itself replays bit-identically):
 
   alive_i  = (i < vocab_limit) AND mask bit i (if a mask row is given)
   s_i      = (logit_i - max_alive) / T          (f32; dead rows -inf; greedy
@@ -22,6 +25,11 @@ so the semantics are defined sort-free):
   greedy rows (T < 1e-5): token = argmax (lowest index wins ties), logprob
              reported at T = 1 over the raw support.
 
+Rows with repetition / presence / frequency penalties or a logit_bias have
+their logits adjusted in place first (ops.apply_logit_penalties; kernel and
+reference ARE bit-identical there), from a device-resident token history
+(penalties.py); the steps above then consume the adjusted logits unchanged.
+
 Per-request seeds (`random_seed_per_input`) use a counter-based SplitMix64
 stream keyed on (seed, step) so results are reproducible independent of batch
 composition.
@@ -34,6 +42,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
+from .penalties import PenaltyState
 from .request import Request
 
 # below this, a temperature is treated as greedy (the reference cloud's
@@ -117,9 +126,13 @@ def sample_torch_reference(
 
 
 class Sampler:
-    def __init__(self, device: str, seed: int = 0, vocab_limit: int = 151936) -> None:
+    def __init__(self, device: str, seed: int = 0, vocab_limit: int = 151936,
+                 penalties: Optional[PenaltyState] = None) -> None:
         self.device = device
         self.vocab_limit = vocab_limit
+        # history pool for penalised rows (owned by the engine, which also
+        # releases slots); None = this sampler cannot serve penalised rows
+        self.penalties = penalties
         self.generator = torch.Generator(device="cpu").manual_seed(seed)
         # per-batch-composition cache of the sampling-param tensors: at steady
         # decode the request set only changes on admit/finish/preempt, so the
@@ -155,8 +168,75 @@ class Sampler:
         seeded = [i for i, r in enumerate(reqs) if r.sampling.seed is not None]
         seeds = np.array([reqs[i].sampling.seed for i in seeded], dtype=np.uint64)
         self._param_key = key
-        self._params = (temps, top_ps, top_ks, unseeded, seeded, seeds)
+        self._params = (temps, top_ps, top_ks, unseeded, seeded, seeds,
+                        self._penalty_params(reqs, device))
         return self._params
+
+    def _penalty_params(self, reqs: List[Request], device) -> Optional[dict]:
+        """Per-composition penalty tensors (None when no row is penalised —
+        the common case, which then costs nothing per step)."""
+        rows = [i for i, r in enumerate(reqs) if r.sampling.penalised]
+        if not rows:
+            return None
+        if self.penalties is None:
+            raise RuntimeError("penalised request but the sampler has no "
+                               "PenaltyState (history pool)")
+        sps = [reqs[i].sampling for i in rows]
+
+        def f32(vals):
+            return torch.tensor(vals, dtype=torch.float32, device=device)
+
+        def i32(vals):
+            return torch.tensor(vals, dtype=torch.int32, device=device)
+
+        pen = {
+            "rows": rows,
+            "row_idx": i32(rows),
+            "prompt_len": i32([reqs[i].num_prompt_tokens for i in rows]),
+            "rep": f32([sp.repetition_penalty for sp in sps]),
+            "pres": f32([sp.presence_penalty for sp in sps]),
+            "freq": f32([sp.frequency_penalty for sp in sps]),
+            "bias_tok": None, "bias_val": None,
+            # slots follow KV residency, so they are re-checked every step
+            "slots": None, "slot_t": None,
+        }
+        n_bias = max(len(sp.logit_bias or ()) for sp in sps)
+        if n_bias:
+            tok = np.full((len(rows), n_bias), -1, dtype=np.int32)
+            val = np.zeros((len(rows), n_bias), dtype=np.float32)
+            for j, sp in enumerate(sps):
+                for k, (t, v) in enumerate((sp.logit_bias or {}).items()):
+                    # ids past int32 can never be < vocab_limit: leave padding
+                    if t < 2 ** 31:
+                        tok[j, k], val[j, k] = t, v
+            pen["bias_tok"] = torch.from_numpy(tok).to(device)
+            pen["bias_val"] = torch.from_numpy(val).to(device)
+        return pen
+
+    def _apply_penalties(self, logits: torch.Tensor, reqs: List[Request],
+                         pen: dict):
+        """Adjust the penalised rows of `logits` in place. Host->device
+        traffic per step is the m history lengths (+ the m slots when a row
+        was re-admitted); returns (slot_t, len_t) for the post-sample
+        history append."""
+        from .. import ops
+
+        st = self.penalties
+        rows = pen["rows"]
+        slots = [st.slot_of(reqs[i]) for i in rows]
+        if slots != pen["slots"]:
+            pen["slots"] = slots
+            pen["slot_t"] = torch.tensor(slots, dtype=torch.int32,
+                                         device=logits.device)
+        lens = [reqs[i].total_len for i in rows]
+        len_t = torch.tensor(lens, dtype=torch.int32, device=logits.device)
+        ops.apply_logit_penalties(
+            logits, pen["row_idx"], st.hist, pen["slot_t"], len_t,
+            pen["prompt_len"], pen["rep"], pen["pres"], pen["freq"],
+            pen["bias_tok"], pen["bias_val"],
+            vocab_limit=min(self.vocab_limit, logits.shape[1]),
+            max_hist_len=max(lens))
+        return pen["slot_t"], len_t
 
     def _uniforms(self, reqs, unseeded, seeded, seeds, steps_override, device, n):
         u = torch.empty(n, dtype=torch.float64)
@@ -197,10 +277,15 @@ class Sampler:
         host copy by one step)."""
         n = logits.shape[0]
         assert n == len(reqs)
-        temps, top_ps, top_ks, unseeded, seeded, seeds = self._param_tensors(
-            reqs, logits.device)
+        temps, top_ps, top_ks, unseeded, seeded, seeds, pen = (
+            self._param_tensors(reqs, logits.device))
         u = self._uniforms(reqs, unseeded, seeded, seeds, steps_override,
                            logits.device, n)
+        if pen is not None:
+            # in place, before mask / temperature / top-k/p. Safe on the
+            # decode graph's static logits buffer too: every replay rewrites
+            # that buffer in full before it is read again.
+            pen_slots, pen_lens = self._apply_penalties(logits, reqs, pen)
 
         if logits.is_cuda:
             tokens, lp = self._sample_hip(logits, temps, top_ps, top_ks, u,
@@ -217,6 +302,9 @@ class Sampler:
                                                           logits.shape[1]))
             tokens, lp = sample_torch_reference(
                 logits, temps, top_ps, top_ks, u, self.vocab_limit, mask_bool)
+        if pen is not None:
+            # the new token joins the row's device history at its position
+            self.penalties.append(pen_slots, pen_lens, tokens[pen["row_idx"]])
         if return_tensors:
             return tokens, lp
         return tokens.tolist(), lp.tolist()

@@ -16,7 +16,7 @@ Invariants:
 from __future__ import annotations
 
 from collections import deque
-from typing import Deque, Dict, List
+from typing import Callable, Deque, Dict, List, Optional
 
 from .batch import ScheduledBatch
 from .config import EngineConfig
@@ -32,6 +32,10 @@ class Scheduler:
         self.waiting_p1: Deque[Request] = deque()
         self.running: List[Request] = []
         self.priorities: Dict[int, int] = {}
+        # called with the request wherever it stops holding KV pages (finish,
+        # abort, preemption): per-request device state tied to residency
+        # (the penalty history slot) is given back here
+        self.on_release: Optional[Callable[[Request], None]] = None
 
     # ---- queue management ----
 
@@ -50,6 +54,11 @@ class Scheduler:
                 q.remove(req)
             except ValueError:
                 pass
+        self._released(req)
+
+    def _released(self, req: Request) -> None:
+        if self.on_release is not None:
+            self.on_release(req)
 
     def has_work(self) -> bool:
         return bool(self.running or self.waiting_p0 or self.waiting_p1)
@@ -59,6 +68,7 @@ class Scheduler:
         if req in self.running:
             self.running.remove(req)
         self.kv.release(req.req_id)
+        self._released(req)
 
     # ---- the step ----
 
@@ -70,6 +80,7 @@ class Scheduler:
                 continue
             self.running.remove(victim)
             self.kv.release(victim.req_id)
+            self._released(victim)
             victim.restart()
             q = self.waiting_p0 if self.priorities.get(victim.req_id, 0) == 0 else self.waiting_p1
             q.appendleft(victim)
@@ -114,6 +125,7 @@ class Scheduler:
                 # could not even hold this one: preempt it too
                 self.running.remove(req)
                 self.kv.release(req.req_id)
+                self._released(req)
                 req.restart()
                 (self.waiting_p0 if self.priorities.get(req.req_id, 0) == 0
                  else self.waiting_p1).appendleft(req)

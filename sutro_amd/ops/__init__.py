@@ -191,3 +191,42 @@ def moe_combine(out, rows, padpos, w):
     contrib = rows[padpos].float()          # [T, k, h]
     out.copy_((contrib * w.unsqueeze(-1)).sum(dim=1).to(out.dtype))
     return out
+
+
+# largest hist_len + bias width one LDS table (16384 entries, half full) holds
+PENALTY_MAX_ENTRIES = 8192
+
+
+def apply_logit_penalties(logits, row_idx, hist, slot, hist_len, prompt_len,
+                          rep, pres, freq, bias_tok=None, bias_val=None,
+                          vocab_limit: Optional[int] = None,
+                          max_hist_len: Optional[int] = None):
+    """In-place repetition/presence/frequency penalties + logit_bias on the
+    rows of `logits` [n, V] listed in `row_idx` (unique; m of them). All
+    tensors live on the logits' device: hist int32 [S, Lcap], slot/hist_len/
+    prompt_len int32 [m], rep/pres/freq f32 [m], bias_tok int32 [m, B] (-1
+    padded) + bias_val f32 [m, B] or None. Semantics: torch_ref.
+    apply_logit_penalties; csrc/logit_penalties.hip matches it bit for bit.
+
+    `max_hist_len` is the caller's host-side bound on hist_len (the engine
+    knows it; it sizes the LDS table). Left None it is read back from the
+    device, which synchronizes. Calls whose hist_len + B exceed one table
+    (> 8192, beyond the default max_model_len) run the torch reference on
+    the device instead."""
+    m = int(row_idx.numel())
+    if m == 0:
+        return logits
+    vl = logits.shape[1] if vocab_limit is None else min(int(vocab_limit),
+                                                         logits.shape[1])
+    if _use_hip(logits):
+        if max_hist_len is None:
+            max_hist_len = int(hist_len.max())
+        n_bias = 0 if bias_tok is None else int(bias_tok.shape[1])
+        if max_hist_len + n_bias <= PENALTY_MAX_ENTRIES:
+            _require_hip().logit_penalties(
+                logits, row_idx, hist, slot, hist_len, prompt_len, rep, pres,
+                freq, bias_tok, bias_val, vl, int(max_hist_len))
+            return logits
+    return torch_ref.apply_logit_penalties(
+        logits, row_idx, hist, slot, hist_len, prompt_len, rep, pres, freq,
+        bias_tok, bias_val, vl)

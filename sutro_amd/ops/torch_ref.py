@@ -165,3 +165,75 @@ def grouped_gemm(out, a, w, row_tok, tile_off, counts, max_tiles, gate_silu,
         else:
             out[s0:s0 + c] = (rows @ w[e].T.float()).to(out.dtype)
     return out
+
+
+def apply_logit_penalties(logits, row_idx, hist, slot, hist_len, prompt_len,
+                          rep, pres, freq, bias_tok, bias_val,
+                          vocab_limit: int):
+    """Reference for csrc/logit_penalties.hip (and the CPU path): in-place
+    repetition / presence / frequency penalties + logit_bias on the rows in
+    `row_idx`. For row r with history h = hist[slot[r], :hist_len[r]], prompt
+    length P and every token t < vocab_limit:
+
+        a(t) = t in h            c(t) = #{ j >= P : h[j] = t }
+        y = f32(x[t])
+        if a(t):    y = y / rep if y > 0 else y * rep
+        y = y - freq * f32(c(t))
+        if c(t)>0:  y = y - pres
+        if t in bias: y = y + bias[t]      (first matching entry of the row)
+        x[t] = y rounded to x's dtype
+
+    Only touched elements (a(t) or t a bias key) are written. Each line is
+    one separately rounded f32 torch op, the sequence the kernel follows, so
+    the two agree bit for bit."""
+    m = int(row_idx.numel())
+    if m == 0:
+        return logits
+    dev = logits.device
+    vl = min(int(vocab_limit), logits.shape[1])
+    lcap = hist.shape[1]
+    rows, slots = row_idx.tolist(), slot.tolist()
+    lens, plens = hist_len.tolist(), prompt_len.tolist()
+    n_bias = 0 if bias_tok is None else int(bias_tok.shape[1])
+    for r in range(m):
+        L = max(0, min(lens[r], lcap))
+        P = max(0, min(plens[r], L))
+        h = hist[slots[r], :L].long()
+        out_pos = torch.arange(L, device=dev) >= P
+        ok = (h >= 0) & (h < vl)
+        h_all, h_out = h[ok], h[ok & out_pos]
+        if n_bias:
+            bt = bias_tok[r].long()
+            b_ok = (bt >= 0) & (bt < vl)
+            b_pos = torch.nonzero(b_ok).squeeze(1)
+            bt = bt[b_ok]
+        else:
+            bt = h_all[:0]
+        toks = torch.unique(torch.cat([h_all, bt]))     # sorted, distinct
+        if toks.numel() == 0:
+            continue
+        cnt = torch.zeros(toks.numel(), dtype=torch.int64, device=dev)
+        cnt.index_add_(0, torch.searchsorted(toks, h_out),
+                       torch.ones_like(h_out))
+        seen = torch.isin(toks, h_all)
+        has_bias = torch.zeros_like(seen)
+        bval = torch.zeros(toks.numel(), dtype=torch.float32, device=dev)
+        if bt.numel():
+            # first entry wins when a key is listed twice
+            first = torch.full((toks.numel(),), n_bias, dtype=torch.int64,
+                               device=dev)
+            first.scatter_reduce_(0, torch.searchsorted(toks, bt), b_pos,
+                                  reduce="amin")
+            has_bias = first < n_bias
+            bval = torch.where(has_bias,
+                               bias_val[r].float()[first.clamp(max=n_bias - 1)],
+                               bval)
+        x = logits[rows[r]]
+        y = x[toks].float()
+        rp, pr, fq = rep[r].float(), pres[r].float(), freq[r].float()
+        y = torch.where(seen, torch.where(y > 0, y / rp, y * rp), y)
+        y = y - fq * cnt.float()
+        y = torch.where(cnt > 0, y - pr, y)
+        y = torch.where(has_bias, y + bval, y)
+        x[toks] = y.to(logits.dtype)
+    return logits

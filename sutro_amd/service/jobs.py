@@ -365,6 +365,9 @@ class JobService:
         desc = payload.get("description")
         if desc and len(desc) > DESC_MAX:
             raise ValueError(f"description exceeds {DESC_MAX} characters")
+        # bad sampling values (penalty ranges, logit_bias shape) are rejected
+        # here, like a quota violation, instead of failing inside a worker
+        SamplingParams.from_dict(payload.get("sampling_params"))
         model = payload["model"]
         try:
             get_model_spec(model)  # validate early
