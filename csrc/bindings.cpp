@@ -57,6 +57,11 @@ void sutro_logit_penalties(void*, int, const int*, const int*, const int*,
                            const int*, const int*, const float*, const float*,
                            const float*, const int*, const float*, int, int,
                            long, int, int, int, int, int, hipStream_t);
+void sutro_quant_rows_fp8(void*, float*, const void*, const int*, int, long,
+                          int, int, hipStream_t);
+void sutro_grouped_gemm_fp8(void*, const void*, const float*, const void*,
+                            const float*, const int*, const int*, const int*,
+                            int, int, int, long, int, int, hipStream_t);
 }
 
 void rmsnorm(torch::Tensor out, torch::Tensor x, torch::Tensor w, double eps) {
@@ -259,6 +264,83 @@ void grouped_gemm(torch::Tensor out, torch::Tensor a, torch::Tensor w,
                      (int)bm, cur_stream());
 }
 
+// bf16 [R, K] -> e4m3 [R, Kp] + f32 scale [R] (Kp = K rounded up to 128, zero
+// tail). row_limit (int32 device scalar) * limit_mul bounds the rows written.
+void quant_rows_fp8(torch::Tensor x, torch::Tensor out_q,
+                    torch::Tensor out_scale,
+                    c10::optional<torch::Tensor> row_limit, long limit_mul) {
+  CHECK_CUDA(x); CHECK_CONTIG(x); CHECK_BF16(x);
+  CHECK_CUDA(out_q); CHECK_CONTIG(out_q);
+  CHECK_CUDA(out_scale); CHECK_CONTIG(out_scale);
+  TORCH_CHECK(x.dim() == 2 && out_q.dim() == 2, "x, out_q must be 2-D");
+  TORCH_CHECK(is_fp8(out_q), "out_q must be float8_e4m3fn");
+  TORCH_CHECK(out_scale.scalar_type() == at::kFloat, "out_scale must be f32");
+  const long R = x.size(0), K = x.size(1), Kp = out_q.size(1);
+  TORCH_CHECK(K % 8 == 0 && K > 0, "K must be a positive multiple of 8");
+  TORCH_CHECK(Kp == (K + 127) / 128 * 128, "out_q width must be K rounded "
+              "up to 128 (K=", K, ", Kp=", Kp, ")");
+  TORCH_CHECK(Kp < (1L << 31), "row too wide");
+  TORCH_CHECK(out_q.size(0) >= R && out_scale.numel() >= R,
+              "out_q/out_scale hold fewer rows than x");
+  const int* lim = nullptr;
+  if (row_limit.has_value()) {
+    CHECK_CUDA(*row_limit);
+    TORCH_CHECK(row_limit->scalar_type() == at::kInt
+                && row_limit->numel() >= 1, "row_limit int32 scalar");
+    lim = row_limit->data_ptr<int>();
+  }
+  sutro_quant_rows_fp8(out_q.data_ptr(), out_scale.data_ptr<float>(),
+                       x.data_ptr(), lim, (int)limit_mul, R, (int)K, (int)Kp,
+                       cur_stream());
+}
+
+void grouped_gemm_fp8(torch::Tensor out, torch::Tensor a_q,
+                      torch::Tensor a_scale, torch::Tensor w_q,
+                      torch::Tensor w_scale,
+                      c10::optional<torch::Tensor> row_tok,
+                      torch::Tensor tile_off, torch::Tensor counts,
+                      long max_tiles, bool gate_silu, long bm) {
+  TORCH_CHECK(bm == 64 || bm == 128, "bm must be 64 or 128");
+  CHECK_CUDA(a_q); CHECK_CONTIG(a_q); CHECK_CUDA(w_q); CHECK_CONTIG(w_q);
+  TORCH_CHECK(is_fp8(a_q) && is_fp8(w_q), "a_q, w_q must be float8_e4m3fn");
+  CHECK_CUDA(a_scale); CHECK_CONTIG(a_scale);
+  CHECK_CUDA(w_scale); CHECK_CONTIG(w_scale);
+  TORCH_CHECK(a_scale.scalar_type() == at::kFloat
+              && w_scale.scalar_type() == at::kFloat, "scales must be f32");
+  CHECK_CUDA(out); CHECK_CONTIG(out); CHECK_BF16(out);
+  TORCH_CHECK(w_q.dim() == 3 && a_q.dim() == 2 && out.dim() == 2, "ranks");
+  const long E = w_q.size(0), N = w_q.size(1), Kp = w_q.size(2);
+  const long n_cols = gate_silu ? N / 2 : N;
+  TORCH_CHECK(Kp % 128 == 0 && Kp > 0 && n_cols % 64 == 0 && n_cols > 0,
+              "grouped_gemm_fp8 needs Kp a multiple of 128 and n_cols of 64 "
+              "(Kp=", Kp, ", n_cols=", n_cols, ")");
+  TORCH_CHECK(a_q.size(1) == Kp, "A Kp mismatch");
+  TORCH_CHECK(out.size(1) == n_cols, "out width mismatch");
+  TORCH_CHECK(max_tiles >= 0 && out.size(0) >= max_tiles * bm,
+              "out holds fewer rows than max_tiles * bm");
+  TORCH_CHECK(w_scale.numel() == E * N, "w_scale must be [E, N]");
+  TORCH_CHECK(tile_off.scalar_type() == at::kInt
+              && counts.scalar_type() == at::kInt, "tile_off/counts int32");
+  TORCH_CHECK(tile_off.numel() == E + 1 && counts.numel() == E, "seg sizes");
+  const int* rt = nullptr;
+  if (row_tok.has_value()) {
+    TORCH_CHECK(row_tok->scalar_type() == at::kInt, "row_tok int32");
+    TORCH_CHECK(row_tok->numel() >= max_tiles * bm, "row_tok too short");
+    rt = row_tok->data_ptr<int>();
+  } else {
+    TORCH_CHECK(a_q.size(0) >= max_tiles * bm,
+                "a_q holds fewer rows than max_tiles * bm");
+  }
+  TORCH_CHECK(!gate_silu || rt, "the gate/up stage gathers through row_tok");
+  TORCH_CHECK(a_scale.numel() >= a_q.size(0), "a_scale shorter than a_q");
+  sutro_grouped_gemm_fp8(out.data_ptr(), a_q.data_ptr(),
+                         a_scale.data_ptr<float>(), w_q.data_ptr(),
+                         w_scale.data_ptr<float>(), rt,
+                         tile_off.data_ptr<int>(), counts.data_ptr<int>(),
+                         (int)E, (int)max_tiles, (int)n_cols, Kp,
+                         gate_silu ? 1 : 0, (int)bm, cur_stream());
+}
+
 void moe_combine(torch::Tensor out, torch::Tensor rows, torch::Tensor padpos,
                  torch::Tensor w) {
   CHECK_CUDA(rows); CHECK_CONTIG(rows); CHECK_BF16(rows);
@@ -390,6 +472,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_combine", &moe_combine, "fused MoE weighted gather-combine");
   m.def("grouped_gemm", &grouped_gemm,
         "dropless MoE grouped GEMM (padded segments, static grid)");
+  m.def("quant_rows_fp8", &quant_rows_fp8,
+        "bf16 rows -> e4m3 codes + f32 per-row scale (K padded to 128)");
+  m.def("grouped_gemm_fp8", &grouped_gemm_fp8,
+        "dropless MoE grouped GEMM, e4m3 operands on the block-scaled MFMA");
   m.def("sampler_fused", &sampler_fused,
         "fused mask+temp+topk/topp+sample+logprob (radix descent, no sort)");
   m.def("logit_penalties", &logit_penalties,

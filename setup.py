@@ -23,6 +23,7 @@ SOURCES = [
     "csrc/gemm_tn.hip",
     "csrc/sampler.hip",
     "csrc/grouped_gemm.hip",
+    "csrc/grouped_gemm_fp8.hip",
     "csrc/logit_penalties.hip",
 ]
 

@@ -187,11 +187,18 @@ def models():
 @click.option("--host", default="127.0.0.1")
 @click.option("--port", default=8000, type=int)
 @click.option("--device", default="auto")
-def serve(host: str, port: int, device: str):
+@click.option("--moe-weight-dtype", default="bf16",
+              type=click.Choice(["bf16", "fp8_e4m3"]),
+              help="storage of MoE expert weights (fp8_e4m3 halves them)")
+def serve(host: str, port: int, device: str, moe_weight_dtype: str):
     """Serve the HTTP API (the same endpoint contract as api.sutro.sh)."""
     from .service.http_api import run_server
 
-    run_server(host=host, port=port, device=device)
+    engine_kwargs = None
+    if moe_weight_dtype != "bf16":
+        engine_kwargs = {"moe_weight_dtype": moe_weight_dtype}
+    run_server(host=host, port=port, device=device,
+               engine_kwargs=engine_kwargs)
 
 
 @cli.command()

@@ -58,8 +58,18 @@ class EngineConfig:
     # MoE layers: shard EXPERTS across the tp group (expert parallelism)
     # instead of sharding every expert's intermediate dim
     moe_ep: bool = False
+    # "bf16" (default) or "fp8_e4m3": store MoE expert weights as OCP e4m3
+    # with f32 per-output-channel scales (quantised after load, per shard)
+    # and run them on the block-scaled fp8 MFMA — halves expert bytes, which
+    # frees memory for KV. Ignored for specs without experts (a service
+    # hands one engine_kwargs to every model).
+    moe_weight_dtype: str = "bf16"
 
     def __post_init__(self) -> None:
+        if self.moe_weight_dtype not in ("bf16", "fp8_e4m3"):
+            raise ValueError(
+                f"moe_weight_dtype must be 'bf16' or 'fp8_e4m3', got "
+                f"{self.moe_weight_dtype!r}")
         if self.device == "cpu":
             self.dtype = torch.float32
         if self.max_model_len > self.spec.max_context:

@@ -93,6 +93,16 @@ class LLMEngine:
             else:
                 model.init_random_weights(cfg.seed)
         self.model = model.to(cfg.device).eval()
+        if cfg.moe_weight_dtype == "fp8_e4m3" and self.spec.num_experts > 0:
+            from ..models.qwen3 import Qwen3MoE
+
+            for mod in self.model.modules():
+                if isinstance(mod, Qwen3MoE):
+                    mod.quantize_experts_fp8()
+            if cfg.device.startswith("cuda"):
+                # hand the freed bf16 experts back to the driver so the KV
+                # sizing below sees them
+                torch.cuda.empty_cache()
 
         num_blocks = cfg.num_kv_blocks
         if num_blocks is None:

@@ -24,7 +24,8 @@ from ..parallel.tp import TPContext
 from .registry import ModelSpec
 
 
-# shared grouped-MoE workspaces: one per (device, dtype, h, m_l, E_local) —
+# shared grouped-MoE workspaces: one per (device, dtype, h, m_l, E_local
+# [, expert weight dtype when it is not the working dtype]) —
 # all layers of a model (and all models with identical shapes) reuse them;
 # sized before hipGraph capture so captured decode steps never allocate
 _MOE_WS: dict = {}
@@ -174,9 +175,64 @@ class Qwen3MoE(nn.Module):
                 torch.empty(spec.num_experts, h, m_l, dtype=dtype))
             _mark_shard(self.down, (spec.num_experts, h, m), 2, tp)
 
+    @property
+    def experts_fp8(self) -> bool:
+        return self.gate_up.dtype == torch.float8_e4m3fn
+
+    @torch.no_grad()
+    def quantize_experts_fp8(self) -> None:
+        """Replace gate_up / down by OCP e4m3 codes [E, N, Kp] (K zero-padded
+        to the 128-element K-tile) plus f32 per-output-channel scales
+        [E, N] (`gate_up_scale`, `down_scale`). Quantises the LOCAL shard,
+        after sharding: TP/EP need no new shard metadata and each rank's
+        partial sum carries its own scales into the existing all-reduce.
+        The bf16 tensor of each projection is freed before the next one is
+        quantised. Idempotent."""
+        if self.experts_fp8:
+            return
+        for name in ("gate_up", "down"):
+            w = getattr(self, name).data.contiguous()
+            E, N, K = w.shape
+            Kp = torch_ref.fp8_padded_k(K)
+            w_q = torch.empty(E, N, Kp, dtype=torch.float8_e4m3fn,
+                              device=w.device)
+            scale = torch.empty(E, N, dtype=torch.float32, device=w.device)
+            ops.quantize_rows_fp8(w.view(E * N, K), w_q.view(E * N, Kp),
+                                  scale.view(-1))
+            del self._parameters[name]
+            del w
+            self.register_buffer(name, w_q)
+            self.register_buffer(name + "_scale", scale)
+
+    def _expert_mlp(self, seg: torch.Tensor, e: int) -> torch.Tensor:
+        """rows `seg` through local expert e (segment-loop paths). In FP8
+        mode this is the kernel's arithmetic emulated: quantised rows, fp32
+        sums, scales after the sum, SwiGLU in fp32, the activation rounded to
+        the working dtype and quantised again."""
+        if not self.experts_fp8:
+            act = ops.silu_mul(seg @ self.gate_up[e].T)
+            return act @ self.down[e].T
+        n = seg.shape[0]
+        m = self.gate_up.shape[1] // 2
+        dev = seg.device
+
+        def quant(rows):
+            q = torch.empty(n, torch_ref.fp8_padded_k(rows.shape[1]),
+                            dtype=torch.float8_e4m3fn, device=dev)
+            s = torch.empty(n, dtype=torch.float32, device=dev)
+            return ops.quantize_rows_fp8(rows.contiguous(), q, s)
+
+        x_q, x_s = quant(seg)
+        y = torch_ref.fp8_linear(x_q, x_s, self.gate_up[e],
+                                 self.gate_up_scale[e])
+        act = (F.silu(y[:, :m]) * y[:, m:]).to(seg.dtype)
+        a_q, a_s = quant(act)
+        return torch_ref.fp8_linear(a_q, a_s, self.down[e],
+                                    self.down_scale[e]).to(seg.dtype)
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if x.is_cuda:
-            if (self._PREFILL_BLASLT_MIN
+            if (self._PREFILL_BLASLT_MIN and not self.experts_fp8
                     and x.shape[0] >= self._PREFILL_BLASLT_MIN
                     and not torch.cuda.is_current_stream_capturing()):
                 # big eager waves: library GEMMs on true segment sizes
@@ -205,8 +261,7 @@ class Qwen3MoE(nn.Module):
                 continue
             if base <= e < base + e_l:  # EP: other ranks own the rest
                 seg = gathered[start:start + n]
-                act = ops.silu_mul(seg @ self.gate_up[e - base].T)
-                out_sorted[start:start + n] = act @ self.down[e - base].T
+                out_sorted[start:start + n] = self._expert_mlp(seg, e - base)
             else:
                 out_sorted[start:start + n] = 0
             start += n
@@ -231,8 +286,7 @@ class Qwen3MoE(nn.Module):
             if c == 0:
                 continue
             seg = sorted_rows[start:start + c]
-            act = ops.silu_mul(seg @ self.gate_up[e].T)
-            out_sorted[start:start + c] = act @ self.down[e].T
+            out_sorted[start:start + c] = self._expert_mlp(seg, e)
             start += c
         out = torch.empty_like(rows)
         out[order] = out_sorted
@@ -311,23 +365,36 @@ class Qwen3MoE(nn.Module):
         h = self.down.shape[1]
         m_l = self.gate_up.shape[1] // 2
         rows_max = T * self.top_k + self.experts_per_rank * self._GG_BM
-        key = (str(dev), self.gate_up.dtype, h, m_l, self.experts_per_rank)
+        fp8 = self.experts_fp8
+        # activations keep the working dtype whatever the experts are stored in
+        dtype = self.router.weight.dtype
+        key = (str(dev), dtype, h, m_l, self.experts_per_rank)
+        if fp8:
+            key += (self.gate_up.dtype,)
         ws = _MOE_WS.get(key)
         if ws is None or ws["rows"] < rows_max or ws["max_T"] < T:
             rows_max = max(rows_max, ws["rows"] if ws else 0)
             T = max(T, ws["max_T"] if ws else 0)
             ws = {
                 "rows": rows_max,
-                "act": torch.empty(rows_max, m_l, dtype=self.gate_up.dtype,
-                                   device=dev),
-                "out_sorted": torch.empty(rows_max, h,
-                                          dtype=self.gate_up.dtype,
+                "act": torch.empty(rows_max, m_l, dtype=dtype, device=dev),
+                "out_sorted": torch.empty(rows_max, h, dtype=dtype,
                                           device=dev),
                 "row_tok": torch.empty(rows_max, dtype=torch.int32,
                                        device=dev),
             }
-            ws["out"] = torch.empty(T, h, dtype=self.gate_up.dtype,
-                                    device=dev)
+            ws["out"] = torch.empty(T, h, dtype=dtype, device=dev)
+            if fp8:
+                # quantised stage inputs + their per-row scales
+                f8 = torch.float8_e4m3fn
+                ws["x_q"] = torch.zeros(T, self.gate_up.shape[2],
+                                        dtype=torch.uint8, device=dev).view(f8)
+                ws["x_scale"] = torch.ones(T, dtype=torch.float32, device=dev)
+                ws["act_q"] = torch.zeros(rows_max, self.down.shape[2],
+                                          dtype=torch.uint8,
+                                          device=dev).view(f8)
+                ws["act_scale"] = torch.ones(rows_max, dtype=torch.float32,
+                                             device=dev)
             # zero once: rows past the padded total are never written, but
             # EP-invalid assignments gather them with weight 0 — torch.empty
             # garbage could be inf/NaN and 0*NaN = NaN
@@ -448,11 +515,26 @@ class Qwen3MoE(nn.Module):
 
         m_l = self.gate_up.shape[1] // 2
         act = ws["act"][:rows_max]
-        ops.grouped_gemm(act, x, self.gate_up, row_tok, tile_off, counts,
-                         max_tiles, True, bm=BM)
         out_sorted = ws["out_sorted"][:rows_max]
-        ops.grouped_gemm(out_sorted, act, self.down, None, tile_off, counts,
-                         max_tiles, False, bm=BM)
+        if self.experts_fp8:
+            # quant(x) -> stage 1 -> quant(act) -> stage 2, all into the
+            # workspace; the second quant stops at the live padded total
+            x_q, x_s = ws["x_q"][:T], ws["x_scale"][:T]
+            ops.quantize_rows_fp8(x.contiguous(), x_q, x_s)
+            ops.grouped_gemm_fp8(act, x_q, x_s, self.gate_up,
+                                 self.gate_up_scale, row_tok, tile_off,
+                                 counts, max_tiles, True, bm=BM)
+            a_q, a_s = ws["act_q"][:rows_max], ws["act_scale"][:rows_max]
+            ops.quantize_rows_fp8(act, a_q, a_s, row_limit=tile_off[E_l:],
+                                  limit_mul=BM)
+            ops.grouped_gemm_fp8(out_sorted, a_q, a_s, self.down,
+                                 self.down_scale, None, tile_off, counts,
+                                 max_tiles, False, bm=BM)
+        else:
+            ops.grouped_gemm(act, x, self.gate_up, row_tok, tile_off, counts,
+                             max_tiles, True, bm=BM)
+            ops.grouped_gemm(out_sorted, act, self.down, None, tile_off,
+                             counts, max_tiles, False, bm=BM)
         # deterministic combine in fixed k-order (no float atomics): map each
         # original (token, j) assignment back to its padded row
         padpos = torch.empty(T * k, dtype=torch.long, device=dev)

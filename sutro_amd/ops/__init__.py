@@ -182,6 +182,36 @@ def grouped_gemm(out, a, w, row_tok, tile_off, counts, max_tiles, gate_silu,
                                   max_tiles, gate_silu, bm)
 
 
+def quantize_rows_fp8(x, out_q, out_scale, row_limit=None, limit_mul=1):
+    """x [R, K] -> e4m3 codes out_q [R, Kp] + f32 per-row scale out_scale [R]
+    (scale = amax/448, Kp = K rounded up to 128 with a zero tail):
+    csrc/grouped_gemm_fp8.hip on GPU (bf16 input), torch reference on CPU —
+    bit-identical. row_limit (int32 device scalar) * limit_mul optionally
+    bounds the rows written, without a host sync on GPU."""
+    if _use_hip(x):
+        _require_hip().quant_rows_fp8(x, out_q, out_scale, row_limit,
+                                      limit_mul)
+        return out_q, out_scale
+    return torch_ref.quantize_rows_fp8(x, out_q, out_scale, row_limit,
+                                       limit_mul)
+
+
+def grouped_gemm_fp8(out, a_q, a_scale, w_q, w_scale, row_tok, tile_off,
+                     counts, max_tiles, gate_silu, bm=64):
+    """`grouped_gemm` with e4m3 operands: a_q [., Kp] + f32 row scales
+    (stage 1: indexed through row_tok), w_q [E, N, Kp] + f32 per-output-
+    channel scales [E, N], bf16 out. Block-scaled MFMA kernel
+    (csrc/grouped_gemm_fp8.hip) on GPU, emulated arithmetic on CPU."""
+    if _use_hip(a_q):
+        _require_hip().grouped_gemm_fp8(out, a_q, a_scale, w_q, w_scale,
+                                        row_tok, tile_off, counts, max_tiles,
+                                        gate_silu, bm)
+        return out
+    return torch_ref.grouped_gemm_fp8(out, a_q, a_scale, w_q, w_scale,
+                                      row_tok, tile_off, counts, max_tiles,
+                                      gate_silu, bm)
+
+
 def moe_combine(out, rows, padpos, w):
     """out[t] = sum_j w[t,j] * rows[padpos[t,j]]: fused bf16 gather-combine
     (csrc/grouped_gemm.hip) on GPU, deterministic torch gather on CPU."""

@@ -167,6 +167,87 @@ def grouped_gemm(out, a, w, row_tok, tile_off, counts, max_tiles, gate_silu,
     return out
 
 
+FP8_E4M3_MAX = 448.0
+
+
+def fp8_padded_k(K: int) -> int:
+    """K rounded up to the 128-element K-tile of csrc/grouped_gemm_fp8.hip."""
+    return (K + 127) // 128 * 128
+
+
+def quantize_rows_fp8(x, out_q, out_scale, row_limit=None, limit_mul: int = 1):
+    """Reference for quant_rows_fp8 (csrc/grouped_gemm_fp8.hip) and the CPU
+    path: x [R, K] -> OCP e4m3 codes out_q [R, Kp] + f32 scale out_scale [R].
+
+        amax  = max_k |f32(x[r, k])|
+        scale = amax / 448            (true f32 division; 1 when amax == 0)
+        code  = e4m3_rne(clamp(f32(x) / scale, -448, 448))   (true division)
+
+    The tail [K, Kp) is zero bytes. Both divisions are tensor / tensor so
+    torch never substitutes a reciprocal multiply; the kernel follows the
+    same sequence and agrees bit for bit. Rows >= row_limit[0] * limit_mul
+    are left untouched when row_limit (an int tensor) is given."""
+    R, K = x.shape
+    if row_limit is not None:
+        R = min(R, int(row_limit.reshape(-1)[0]) * limit_mul)
+    xf = x[:R].float()
+    amax = xf.abs().amax(dim=1)
+    scale = torch.where(amax > 0, amax / torch.full_like(amax, FP8_E4M3_MAX),
+                        torch.ones_like(amax))
+    q = (xf / scale.unsqueeze(1)).clamp(-FP8_E4M3_MAX, FP8_E4M3_MAX)
+    qb = out_q.view(torch.uint8)
+    qb[:R, :K] = q.to(torch.float8_e4m3fn).view(torch.uint8)
+    qb[:R, K:] = 0
+    out_scale[:R] = scale
+    return out_q, out_scale
+
+
+def quantize_weight_fp8(w):
+    """w [E, N, K] -> (w_q [E, N, Kp] e4m3, scale [E, N] f32): one scale per
+    output channel, K zero-padded to the kernel's 128-element K-tile."""
+    E, N, K = w.shape
+    Kp = fp8_padded_k(K)
+    w_q = torch.empty(E, N, Kp, dtype=torch.float8_e4m3fn, device=w.device)
+    scale = torch.empty(E, N, dtype=torch.float32, device=w.device)
+    quantize_rows_fp8(w.reshape(E * N, K), w_q.view(E * N, Kp), scale.view(-1))
+    return w_q, scale
+
+
+def fp8_linear(a_q, a_scale, w_q, w_scale):
+    """Emulated e4m3 GEMM: (a_q @ w_q^T in fp32) * a_scale[:, None]
+    * w_scale[None, :] -> fp32 [rows, N]. Scales are applied after the sum,
+    in the kernel epilogue's order."""
+    acc = a_q.float() @ w_q.float().T
+    return acc * a_scale.unsqueeze(1) * w_scale.unsqueeze(0)
+
+
+def grouped_gemm_fp8(out, a_q, a_scale, w_q, w_scale, row_tok, tile_off,
+                     counts, max_tiles, gate_silu, bm: int = 64):
+    """Reference for grouped_gemm_fp8 (csrc/grouped_gemm_fp8.hip) and the CPU
+    path: the layout contract of `grouped_gemm` with the quantised arithmetic
+    emulated — e4m3 codes, products and sums in fp32, scales after the sum,
+    SwiGLU in fp32, then one rounding to out's dtype. Padding rows of `out`
+    are left untouched."""
+    E, N, _ = w_q.shape
+    n_cols = N // 2 if gate_silu else N
+    for e in range(E):
+        c = int(counts[e])
+        if c == 0:
+            continue
+        s0 = int(tile_off[e]) * bm
+        if row_tok is not None:
+            idx = row_tok[s0:s0 + c].long().clamp(min=0)
+        else:
+            idx = torch.arange(s0, s0 + c, device=a_q.device)
+        # index the byte view: fp8 tensors have no gather kernels everywhere
+        rows = a_q.view(torch.uint8)[idx].view(torch.float8_e4m3fn)
+        y = fp8_linear(rows, a_scale[idx], w_q[e], w_scale[e])
+        if gate_silu:
+            y = torch.nn.functional.silu(y[:, :n_cols]) * y[:, n_cols:]
+        out[s0:s0 + c] = y.to(out.dtype)
+    return out
+
+
 def apply_logit_penalties(logits, row_idx, hist, slot, hist_len, prompt_len,
                           rep, pres, freq, bias_tok, bias_val,
                           vocab_limit: int):

@@ -219,8 +219,10 @@ def create_app(home: Optional[str] = None, device: str = "auto",
 
 
 def run_server(host: str = "127.0.0.1", port: int = 8000, device: str = "auto",
-               home: Optional[str] = None, api_keys: Optional[set] = None):
+               home: Optional[str] = None, api_keys: Optional[set] = None,
+               engine_kwargs: Optional[dict] = None):
     import uvicorn
 
-    uvicorn.run(create_app(home=home, device=device, api_keys=api_keys),
+    uvicorn.run(create_app(home=home, device=device, api_keys=api_keys,
+                           engine_kwargs=engine_kwargs),
                 host=host, port=port)
