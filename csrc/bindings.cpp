@@ -62,6 +62,11 @@ void sutro_quant_rows_fp8(void*, float*, const void*, const int*, int, long,
 void sutro_grouped_gemm_fp8(void*, const void*, const float*, const void*,
                             const float*, const int*, const int*, const int*,
                             int, int, int, long, int, int, hipStream_t);
+void sutro_quant_weight_mxfp4(void*, void*, const void*, long, int, int,
+                              hipStream_t);
+void sutro_grouped_gemm_mxfp4(void*, const void*, const float*, const void*,
+                              const void*, const int*, const int*, const int*,
+                              int, int, int, long, int, int, hipStream_t);
 }
 
 void rmsnorm(torch::Tensor out, torch::Tensor x, torch::Tensor w, double eps) {
@@ -341,6 +346,83 @@ void grouped_gemm_fp8(torch::Tensor out, torch::Tensor a_q,
                          gate_silu ? 1 : 0, (int)bm, cur_stream());
 }
 
+// bf16 [R, K] -> MXFP4: e2m1 codes u8 [R, Kp/2] (two per byte, low nibble
+// first) + e8m0 block scales u8 [R, Kp/32]; Kp = K rounded up to 128.
+void quant_weight_mxfp4(torch::Tensor x, torch::Tensor out_q,
+                        torch::Tensor out_scale) {
+  CHECK_CUDA(x); CHECK_CONTIG(x); CHECK_BF16(x);
+  CHECK_CUDA(out_q); CHECK_CONTIG(out_q);
+  CHECK_CUDA(out_scale); CHECK_CONTIG(out_scale);
+  TORCH_CHECK(x.dim() == 2 && out_q.dim() == 2 && out_scale.dim() == 2,
+              "x, out_q, out_scale must be 2-D");
+  TORCH_CHECK(out_q.scalar_type() == at::kByte
+              && out_scale.scalar_type() == at::kByte,
+              "out_q, out_scale must be uint8");
+  const long R = x.size(0), K = x.size(1);
+  TORCH_CHECK(K % 8 == 0 && K > 0, "K must be a positive multiple of 8");
+  const long Kp = (K + 127) / 128 * 128;
+  TORCH_CHECK(Kp < (1L << 31), "row too wide");
+  TORCH_CHECK(out_q.size(1) == Kp / 2 && out_scale.size(1) == Kp / 32,
+              "out_q / out_scale widths must be Kp/2 and Kp/32 with Kp = K "
+              "rounded up to 128 (K=", K, ", Kp=", Kp, ")");
+  TORCH_CHECK(out_q.size(0) == R && out_scale.size(0) == R,
+              "out_q/out_scale rows differ from x");
+  sutro_quant_weight_mxfp4(out_q.data_ptr(), out_scale.data_ptr(),
+                           x.data_ptr(), R, (int)K, (int)Kp, cur_stream());
+}
+
+void grouped_gemm_mxfp4(torch::Tensor out, torch::Tensor a_q,
+                        torch::Tensor a_scale, torch::Tensor w_q,
+                        torch::Tensor w_scale,
+                        c10::optional<torch::Tensor> row_tok,
+                        torch::Tensor tile_off, torch::Tensor counts,
+                        long max_tiles, bool gate_silu, long bm) {
+  TORCH_CHECK(bm == 64 || bm == 128, "bm must be 64 or 128");
+  CHECK_CUDA(a_q); CHECK_CONTIG(a_q); CHECK_CUDA(w_q); CHECK_CONTIG(w_q);
+  TORCH_CHECK(is_fp8(a_q), "a_q must be float8_e4m3fn");
+  CHECK_CUDA(a_scale); CHECK_CONTIG(a_scale);
+  CHECK_CUDA(w_scale); CHECK_CONTIG(w_scale);
+  TORCH_CHECK(a_scale.scalar_type() == at::kFloat, "a_scale must be f32");
+  TORCH_CHECK(w_q.scalar_type() == at::kByte
+              && w_scale.scalar_type() == at::kByte,
+              "w_q (e2m1 pairs) and w_scale (e8m0) must be uint8");
+  CHECK_CUDA(out); CHECK_CONTIG(out); CHECK_BF16(out);
+  TORCH_CHECK(w_q.dim() == 3 && w_scale.dim() == 3 && a_q.dim() == 2
+              && out.dim() == 2, "ranks");
+  const long E = w_q.size(0), N = w_q.size(1), Kp = w_q.size(2) * 2;
+  const long n_cols = gate_silu ? N / 2 : N;
+  TORCH_CHECK(Kp % 128 == 0 && Kp > 0 && n_cols % 64 == 0 && n_cols > 0,
+              "grouped_gemm_mxfp4 needs Kp a multiple of 128 and n_cols of 64 "
+              "(Kp=", Kp, ", n_cols=", n_cols, ")");
+  TORCH_CHECK(!gate_silu || N == 2 * n_cols, "gate/up needs an even N");
+  TORCH_CHECK(a_q.size(1) == Kp, "A Kp mismatch");
+  TORCH_CHECK(out.size(1) == n_cols, "out width mismatch");
+  TORCH_CHECK(max_tiles >= 0 && out.size(0) >= max_tiles * bm,
+              "out holds fewer rows than max_tiles * bm");
+  TORCH_CHECK(w_scale.size(0) == E && w_scale.size(1) == N
+              && w_scale.size(2) == Kp / 32, "w_scale must be [E, N, Kp/32]");
+  TORCH_CHECK(tile_off.scalar_type() == at::kInt
+              && counts.scalar_type() == at::kInt, "tile_off/counts int32");
+  TORCH_CHECK(tile_off.numel() == E + 1 && counts.numel() == E, "seg sizes");
+  const int* rt = nullptr;
+  if (row_tok.has_value()) {
+    TORCH_CHECK(row_tok->scalar_type() == at::kInt, "row_tok int32");
+    TORCH_CHECK(row_tok->numel() >= max_tiles * bm, "row_tok too short");
+    rt = row_tok->data_ptr<int>();
+  } else {
+    TORCH_CHECK(a_q.size(0) >= max_tiles * bm,
+                "a_q holds fewer rows than max_tiles * bm");
+  }
+  TORCH_CHECK(!gate_silu || rt, "the gate/up stage gathers through row_tok");
+  TORCH_CHECK(a_scale.numel() >= a_q.size(0), "a_scale shorter than a_q");
+  sutro_grouped_gemm_mxfp4(out.data_ptr(), a_q.data_ptr(),
+                           a_scale.data_ptr<float>(), w_q.data_ptr(),
+                           w_scale.data_ptr(), rt,
+                           tile_off.data_ptr<int>(), counts.data_ptr<int>(),
+                           (int)E, (int)max_tiles, (int)n_cols, Kp,
+                           gate_silu ? 1 : 0, (int)bm, cur_stream());
+}
+
 void moe_combine(torch::Tensor out, torch::Tensor rows, torch::Tensor padpos,
                  torch::Tensor w) {
   CHECK_CUDA(rows); CHECK_CONTIG(rows); CHECK_BF16(rows);
@@ -476,6 +558,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "bf16 rows -> e4m3 codes + f32 per-row scale (K padded to 128)");
   m.def("grouped_gemm_fp8", &grouped_gemm_fp8,
         "dropless MoE grouped GEMM, e4m3 operands on the block-scaled MFMA");
+  m.def("quant_weight_mxfp4", &quant_weight_mxfp4,
+        "bf16 rows -> e2m1 code pairs + e8m0 scale per 32 (K padded to 128)");
+  m.def("grouped_gemm_mxfp4", &grouped_gemm_mxfp4,
+        "dropless MoE grouped GEMM, e4m3 x MXFP4 on the block-scaled MFMA");
   m.def("sampler_fused", &sampler_fused,
         "fused mask+temp+topk/topp+sample+logprob (radix descent, no sort)");
   m.def("logit_penalties", &logit_penalties,

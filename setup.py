@@ -24,6 +24,7 @@ SOURCES = [
     "csrc/sampler.hip",
     "csrc/grouped_gemm.hip",
     "csrc/grouped_gemm_fp8.hip",
+    "csrc/grouped_gemm_mxfp4.hip",
     "csrc/logit_penalties.hip",
 ]
 

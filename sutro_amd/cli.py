@@ -188,8 +188,9 @@ def models():
 @click.option("--port", default=8000, type=int)
 @click.option("--device", default="auto")
 @click.option("--moe-weight-dtype", default="bf16",
-              type=click.Choice(["bf16", "fp8_e4m3"]),
-              help="storage of MoE expert weights (fp8_e4m3 halves them)")
+              type=click.Choice(["bf16", "fp8_e4m3", "mxfp4"]),
+              help="storage of MoE expert weights (fp8_e4m3 halves them, "
+                   "mxfp4 stores 4.25 bits per weight)")
 def serve(host: str, port: int, device: str, moe_weight_dtype: str):
     """Serve the HTTP API (the same endpoint contract as api.sutro.sh)."""
     from .service.http_api import run_server

@@ -63,13 +63,15 @@ class EngineConfig:
     # and run them on the block-scaled fp8 MFMA — halves expert bytes, which
     # frees memory for KV. Ignored for specs without experts (a service
     # hands one engine_kwargs to every model).
+    # "mxfp4": OCP MX e2m1 codes with one e8m0 scale per 32 K-elements (4.25
+    # bits per weight), dequantised inside the block-scaled MFMA (W4A8).
     moe_weight_dtype: str = "bf16"
 
     def __post_init__(self) -> None:
-        if self.moe_weight_dtype not in ("bf16", "fp8_e4m3"):
+        if self.moe_weight_dtype not in ("bf16", "fp8_e4m3", "mxfp4"):
             raise ValueError(
-                f"moe_weight_dtype must be 'bf16' or 'fp8_e4m3', got "
-                f"{self.moe_weight_dtype!r}")
+                f"moe_weight_dtype must be 'bf16', 'fp8_e4m3' or 'mxfp4', "
+                f"got {self.moe_weight_dtype!r}")
         if self.device == "cpu":
             self.dtype = torch.float32
         if self.max_model_len > self.spec.max_context:

@@ -89,16 +89,21 @@ class LLMEngine:
             if cfg.weights_path:
                 from ..models.loader import load_weights
 
-                load_weights(model, cfg.weights_path)
+                load_weights(model, cfg.weights_path,
+                             moe_weight_dtype=cfg.moe_weight_dtype)
             else:
                 model.init_random_weights(cfg.seed)
         self.model = model.to(cfg.device).eval()
-        if cfg.moe_weight_dtype == "fp8_e4m3" and self.spec.num_experts > 0:
+        if cfg.moe_weight_dtype != "bf16" and self.spec.num_experts > 0:
             from ..models.qwen3 import Qwen3MoE
 
             for mod in self.model.modules():
                 if isinstance(mod, Qwen3MoE):
-                    mod.quantize_experts_fp8()
+                    if cfg.moe_weight_dtype == "mxfp4":
+                        # a no-op on experts loaded pre-quantised
+                        mod.quantize_experts_mxfp4()
+                    else:
+                        mod.quantize_experts_fp8()
             if cfg.device.startswith("cuda"):
                 # hand the freed bf16 experts back to the driver so the KV
                 # sizing below sees them

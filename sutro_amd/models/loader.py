@@ -10,6 +10,14 @@ Accepted checkpoint names: this framework's own `named_parameters()` names,
 plus the conventional HF-style aliases (model.layers.N..., model.embed_tokens,
 lm_head) mapped onto them. Merged projections (qkv_proj, gate_up_proj) also
 accept split q/k/v and gate/up tensors.
+
+MXFP4 experts (`moe_weight_dtype="mxfp4"`): `save_weights` writes quantised
+experts as the uint8 pair `<...>.mlp.gate_up_blocks` / `.gate_up_scales` and
+`.down_blocks` / `.down_scales` (the format of
+`torch_ref.quantize_weight_mxfp4`), and `load_weights(...,
+moe_weight_dtype="mxfp4")` copies such a pair into the model bit for bit,
+without a bf16 stage. The pair must have the shape of the local shard (it is
+not re-sliced for TP/EP). The published gpt-oss tensor names are not mapped.
 """
 
 from __future__ import annotations
@@ -19,6 +27,9 @@ import re
 from typing import Dict, Iterator, List, Tuple
 
 import torch
+
+# pre-quantised MXFP4 experts: ...mlp.<gate_up|down>_<blocks|scales>
+_MXFP4_RE = re.compile(r"^(.*\.mlp)\.(gate_up|down)_(blocks|scales)$")
 
 # HF per-expert tensors: ...mlp.experts.<E>.<gate|up|down>_proj.weight
 _EXPERT_RE = re.compile(r"^(.*\.mlp)\.experts\.(\d+)\.(gate|up|down)_proj\.weight$")
@@ -58,9 +69,15 @@ def _shard_slice(p: torch.nn.Parameter, full: torch.Tensor) -> torch.Tensor:
     return torch.cat(parts, dim=dim)
 
 
-def load_weights(model: torch.nn.Module, path: str, strict: bool = True) -> int:
-    """Fill `model` from a safetensors dir. Returns #parameters loaded."""
+def load_weights(model: torch.nn.Module, path: str, strict: bool = True,
+                 moe_weight_dtype: str = "bf16") -> int:
+    """Fill `model` from a safetensors dir. Returns #parameters loaded.
+    With moe_weight_dtype="mxfp4" a checkpoint may hold experts as the
+    quantised uint8 pair (see the module docstring); bf16 experts are loaded
+    as always and left for the engine to quantise."""
     params: Dict[str, torch.nn.Parameter] = dict(model.named_parameters())
+    modules = dict(model.named_modules())
+    pending_mxfp4: Dict[Tuple[str, str], Dict[str, torch.Tensor]] = {}
     pending_merge: Dict[str, Dict[str, torch.Tensor]] = {}
     loaded = set()
 
@@ -89,6 +106,15 @@ def load_weights(model: torch.nn.Module, path: str, strict: bool = True) -> int:
         name = _canon(raw_name)
         if name in params:
             assign(name, tensor)
+            continue
+        mm = _MXFP4_RE.match(name)
+        if mm and f"{mm.group(1)}.{mm.group(2)}" in params:
+            if moe_weight_dtype != "mxfp4":
+                raise ValueError(
+                    f"checkpoint holds MXFP4 experts ({raw_name}); load it "
+                    f"with moe_weight_dtype='mxfp4', not {moe_weight_dtype!r}")
+            pending_mxfp4.setdefault((mm.group(1), mm.group(2)), {})[
+                mm.group(3)] = tensor
             continue
         em = _EXPERT_RE.match(name)
         if em and f"{em.group(1)}.gate_up" in params:
@@ -135,6 +161,14 @@ def load_weights(model: torch.nn.Module, path: str, strict: bool = True) -> int:
                         f"incomplete expert tensors for {prefix} expert {e}")
             assign(pname, torch.stack(full_e))
 
+    for (prefix, which), pair in pending_mxfp4.items():
+        if sorted(pair) != ["blocks", "scales"]:
+            raise ValueError(f"incomplete MXFP4 pair for {prefix}.{which}: "
+                             f"{sorted(pair)}")
+        modules[prefix].load_expert_mxfp4(which, pair["blocks"],
+                                          pair["scales"])
+        loaded.add(f"{prefix}.{which}")
+
     if unexpected and strict:
         raise ValueError(
             f"checkpoint has {len(unexpected)} tensors that map to no "
@@ -156,5 +190,12 @@ def save_weights(model: torch.nn.Module, path: str) -> str:
     out = os.path.join(path, "model.safetensors")
     state = {k: v.detach().cpu().contiguous()
              for k, v in model.named_parameters()}
+    for prefix, mod in model.named_modules():
+        if getattr(mod, "experts_mxfp4", False):
+            for which in ("gate_up", "down"):
+                state[f"{prefix}.{which}_blocks"] = (
+                    getattr(mod, which).detach().cpu().contiguous())
+                state[f"{prefix}.{which}_scales"] = (
+                    getattr(mod, which + "_scales").detach().cpu().contiguous())
     save_file(state, out)
     return out

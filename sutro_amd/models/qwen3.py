@@ -179,6 +179,65 @@ class Qwen3MoE(nn.Module):
     def experts_fp8(self) -> bool:
         return self.gate_up.dtype == torch.float8_e4m3fn
 
+    @property
+    def experts_mxfp4(self) -> bool:
+        return self.gate_up.dtype == torch.uint8
+
+    @torch.no_grad()
+    def quantize_experts_mxfp4(self) -> None:
+        """Replace gate_up / down by MXFP4: e2m1 code pairs uint8
+        [E, N, Kp/2] under the same names plus e8m0 block scales uint8
+        [E, N, Kp/32] (`gate_up_scales`, `down_scales`) — the format of
+        torch_ref.quantize_weight_mxfp4. Like quantize_experts_fp8 it acts
+        on the LOCAL shard after TP/EP sharding and frees the bf16 tensor of
+        each projection before the next one is quantised. Idempotent; refuses
+        to run on FP8 experts (their bf16 source is gone)."""
+        if self.experts_fp8:
+            raise RuntimeError("experts are already quantised to fp8_e4m3; "
+                               "mxfp4 needs the unquantised weights")
+        for name in ("gate_up", "down"):
+            if getattr(self, name).dtype == torch.uint8:
+                continue  # done before, or loaded pre-quantised
+            w = getattr(self, name).data.contiguous()
+            codes, scales = ops.quantize_weight_mxfp4(w)
+            del self._parameters[name]
+            del w
+            self.register_buffer(name, codes)
+            self.register_buffer(name + "_scales", scales)
+
+    @torch.no_grad()
+    def load_expert_mxfp4(self, name: str, codes: torch.Tensor,
+                          scales: torch.Tensor) -> None:
+        """Install a pre-quantised projection (`gate_up` or `down`) of the
+        local shard, bit for bit: the bf16 parameter is dropped unread."""
+        if self.experts_fp8:
+            raise RuntimeError("experts are already quantised to fp8_e4m3")
+        w = getattr(self, name)
+        E, N = w.shape[:2]
+        Kp = (w.shape[2] * 2 if w.dtype == torch.uint8
+              else torch_ref.fp8_padded_k(w.shape[2]))
+        if (codes.dtype != torch.uint8 or scales.dtype != torch.uint8
+                or tuple(codes.shape) != (E, N, Kp // 2)
+                or tuple(scales.shape) != (E, N, Kp // 32)):
+            raise ValueError(
+                f"MXFP4 pair for {name} must be uint8 {(E, N, Kp // 2)} / "
+                f"{(E, N, Kp // 32)} (the local shard), got "
+                f"{codes.dtype} {tuple(codes.shape)} / "
+                f"{scales.dtype} {tuple(scales.shape)}")
+        dev = w.device
+        self._parameters.pop(name, None)
+        self._buffers.pop(name, None)
+        self._buffers.pop(name + "_scales", None)
+        del w
+        self.register_buffer(name, codes.to(dev).contiguous())
+        self.register_buffer(name + "_scales", scales.to(dev).contiguous())
+
+    def _expert_k(self, name: str) -> int:
+        """padded K (elements) of a quantised expert tensor: MXFP4 stores two
+        codes per byte, FP8 one"""
+        w = getattr(self, name)
+        return w.shape[2] * 2 if self.experts_mxfp4 else w.shape[2]
+
     @torch.no_grad()
     def quantize_experts_fp8(self) -> None:
         """Replace gate_up / down by OCP e4m3 codes [E, N, Kp] (K zero-padded
@@ -190,6 +249,9 @@ class Qwen3MoE(nn.Module):
         quantised. Idempotent."""
         if self.experts_fp8:
             return
+        if self.experts_mxfp4:
+            raise RuntimeError("experts are already quantised to mxfp4; "
+                               "fp8_e4m3 needs the unquantised weights")
         for name in ("gate_up", "down"):
             w = getattr(self, name).data.contiguous()
             E, N, K = w.shape
@@ -208,8 +270,10 @@ class Qwen3MoE(nn.Module):
         """rows `seg` through local expert e (segment-loop paths). In FP8
         mode this is the kernel's arithmetic emulated: quantised rows, fp32
         sums, scales after the sum, SwiGLU in fp32, the activation rounded to
-        the working dtype and quantised again."""
-        if not self.experts_fp8:
+        the working dtype and quantised again. MXFP4 mode is the same with
+        exactly dequantised weights and no weight-side epilogue scale."""
+        mx = self.experts_mxfp4
+        if not (self.experts_fp8 or mx):
             act = ops.silu_mul(seg @ self.gate_up[e].T)
             return act @ self.down[e].T
         n = seg.shape[0]
@@ -223,16 +287,24 @@ class Qwen3MoE(nn.Module):
             return ops.quantize_rows_fp8(rows.contiguous(), q, s)
 
         x_q, x_s = quant(seg)
-        y = torch_ref.fp8_linear(x_q, x_s, self.gate_up[e],
-                                 self.gate_up_scale[e])
+        if mx:
+            y = torch_ref.mxfp4_linear(x_q, x_s, self.gate_up[e],
+                                       self.gate_up_scales[e])
+        else:
+            y = torch_ref.fp8_linear(x_q, x_s, self.gate_up[e],
+                                     self.gate_up_scale[e])
         act = (F.silu(y[:, :m]) * y[:, m:]).to(seg.dtype)
         a_q, a_s = quant(act)
+        if mx:
+            return torch_ref.mxfp4_linear(a_q, a_s, self.down[e],
+                                          self.down_scales[e]).to(seg.dtype)
         return torch_ref.fp8_linear(a_q, a_s, self.down[e],
                                     self.down_scale[e]).to(seg.dtype)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if x.is_cuda:
-            if (self._PREFILL_BLASLT_MIN and not self.experts_fp8
+            if (self._PREFILL_BLASLT_MIN
+                    and not (self.experts_fp8 or self.experts_mxfp4)
                     and x.shape[0] >= self._PREFILL_BLASLT_MIN
                     and not torch.cuda.is_current_stream_capturing()):
                 # big eager waves: library GEMMs on true segment sizes
@@ -365,7 +437,7 @@ class Qwen3MoE(nn.Module):
         h = self.down.shape[1]
         m_l = self.gate_up.shape[1] // 2
         rows_max = T * self.top_k + self.experts_per_rank * self._GG_BM
-        fp8 = self.experts_fp8
+        fp8 = self.experts_fp8 or self.experts_mxfp4
         # activations keep the working dtype whatever the experts are stored in
         dtype = self.router.weight.dtype
         key = (str(dev), dtype, h, m_l, self.experts_per_rank)
@@ -387,10 +459,10 @@ class Qwen3MoE(nn.Module):
             if fp8:
                 # quantised stage inputs + their per-row scales
                 f8 = torch.float8_e4m3fn
-                ws["x_q"] = torch.zeros(T, self.gate_up.shape[2],
+                ws["x_q"] = torch.zeros(T, self._expert_k("gate_up"),
                                         dtype=torch.uint8, device=dev).view(f8)
                 ws["x_scale"] = torch.ones(T, dtype=torch.float32, device=dev)
-                ws["act_q"] = torch.zeros(rows_max, self.down.shape[2],
+                ws["act_q"] = torch.zeros(rows_max, self._expert_k("down"),
                                           dtype=torch.uint8,
                                           device=dev).view(f8)
                 ws["act_scale"] = torch.ones(rows_max, dtype=torch.float32,
@@ -516,7 +588,21 @@ class Qwen3MoE(nn.Module):
         m_l = self.gate_up.shape[1] // 2
         act = ws["act"][:rows_max]
         out_sorted = ws["out_sorted"][:rows_max]
-        if self.experts_fp8:
+        if self.experts_mxfp4:
+            # the fp8 sequence with MXFP4 weights (W4A8): same activation
+            # quantiser, same workspace buffers
+            x_q, x_s = ws["x_q"][:T], ws["x_scale"][:T]
+            ops.quantize_rows_fp8(x.contiguous(), x_q, x_s)
+            ops.grouped_gemm_mxfp4(act, x_q, x_s, self.gate_up,
+                                   self.gate_up_scales, row_tok, tile_off,
+                                   counts, max_tiles, True, bm=BM)
+            a_q, a_s = ws["act_q"][:rows_max], ws["act_scale"][:rows_max]
+            ops.quantize_rows_fp8(act, a_q, a_s, row_limit=tile_off[E_l:],
+                                  limit_mul=BM)
+            ops.grouped_gemm_mxfp4(out_sorted, a_q, a_s, self.down,
+                                   self.down_scales, None, tile_off, counts,
+                                   max_tiles, False, bm=BM)
+        elif self.experts_fp8:
             # quant(x) -> stage 1 -> quant(act) -> stage 2, all into the
             # workspace; the second quant stops at the live padded total
             x_q, x_s = ws["x_q"][:T], ws["x_scale"][:T]

@@ -212,6 +212,40 @@ def grouped_gemm_fp8(out, a_q, a_scale, w_q, w_scale, row_tok, tile_off,
                                       gate_silu, bm)
 
 
+def quantize_weight_mxfp4(w):
+    """w [..., K] -> MXFP4 (e2m1 code pairs uint8 [..., Kp/2], e8m0 block
+    scales uint8 [..., Kp/32]); the format and rule are stated in
+    torch_ref.quantize_weight_mxfp4. csrc/grouped_gemm_mxfp4.hip on GPU (bf16
+    input), torch reference on CPU — bit-identical."""
+    if _use_hip(w):
+        *lead, K = w.shape
+        Kp = torch_ref.fp8_padded_k(K)
+        w2 = w.contiguous().view(-1, K)
+        codes = torch.empty(w2.shape[0], Kp // 2, dtype=torch.uint8,
+                            device=w.device)
+        scales = torch.empty(w2.shape[0], Kp // 32, dtype=torch.uint8,
+                             device=w.device)
+        _require_hip().quant_weight_mxfp4(w2, codes, scales)
+        return codes.view(*lead, Kp // 2), scales.view(*lead, Kp // 32)
+    return torch_ref.quantize_weight_mxfp4(w)
+
+
+def grouped_gemm_mxfp4(out, a_q, a_scale, codes, scales, row_tok, tile_off,
+                       counts, max_tiles, gate_silu, bm=64):
+    """`grouped_gemm_fp8` with MXFP4 weights (W4A8): a_q [., Kp] e4m3 + f32
+    row scales, codes [E, N, Kp/2] + e8m0 block scales [E, N, Kp/32], bf16
+    out. Block-scaled MFMA kernel (csrc/grouped_gemm_mxfp4.hip) on GPU,
+    emulated arithmetic on CPU."""
+    if _use_hip(a_q):
+        _require_hip().grouped_gemm_mxfp4(out, a_q, a_scale, codes, scales,
+                                          row_tok, tile_off, counts,
+                                          max_tiles, gate_silu, bm)
+        return out
+    return torch_ref.grouped_gemm_mxfp4(out, a_q, a_scale, codes, scales,
+                                        row_tok, tile_off, counts, max_tiles,
+                                        gate_silu, bm)
+
+
 def moe_combine(out, rows, padpos, w):
     """out[t] = sum_j w[t,j] * rows[padpos[t,j]]: fused bf16 gather-combine
     (csrc/grouped_gemm.hip) on GPU, deterministic torch gather on CPU."""

@@ -248,6 +248,104 @@ def grouped_gemm_fp8(out, a_q, a_scale, w_q, w_scale, row_tok, tile_off,
     return out
 
 
+# the e2m1 grid, indexed by the 3 magnitude bits of a code (bit 3 = sign)
+E2M1_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def quantize_weight_mxfp4(w):
+    """THE statement of the MXFP4 weight format; quant_weight_mxfp4
+    (csrc/grouped_gemm_mxfp4.hip), the GEMM kernel and the loader agree with
+    it bit for bit. w [..., K] (finite) -> (codes uint8 [..., Kp/2],
+    scales uint8 [..., Kp/32]), Kp = fp8_padded_k(K).
+
+    Codes are OCP e2m1 (sign bit 3, magnitude bits index the grid
+    {0, .5, 1, 1.5, 2, 3, 4, 6}), two per byte: element 2i in the low nibble
+    of byte i. Scales are e8m0, value 2^(b-127); one covers 32 consecutive K
+    elements. Rule (OCP MX v1.0), per 32-block, elements past K counting 0:
+
+        amax = max |f32(w)|
+        b    = clamp(floor(log2(amax)) - 2 + 127, 0, 254)   (127 if amax == 0)
+        code = e2m1_rne(clamp(f32(w) / 2^(b-127), -6, 6))
+
+    floor(log2(amax)) is read off the f32 exponent field (subnormal amax
+    clamps to b = 0 either way); the division is the exact multiplication by
+    2^(127-b); rounding is to nearest with ties to the even code (0.25 -> 0,
+    0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4); a value
+    that rounds to zero gets code 0, never the negative zero 8. It follows
+    that codes in [K, Kp) are 0 and that blocks wholly inside the padding
+    tail (and all-zero blocks) hold b = 127 = 0x7f. There is no other weight
+    scale."""
+    *lead, K = w.shape
+    Kp = fp8_padded_k(K)
+    wf = torch.zeros(*lead, Kp, dtype=torch.float32, device=w.device)
+    wf[..., :K] = w.float()
+    blk = wf.view(*lead, Kp // 32, 32)
+    amax = blk.abs().amax(dim=-1)
+    ef = (amax.view(torch.int32) >> 23) & 0xff
+    b = torch.where(amax > 0, (ef - 2).clamp(min=0), torch.full_like(ef, 127))
+    inv = ((254 - b) << 23).view(torch.float32)            # 2^(127-b), exact
+    x = (blk * inv.unsqueeze(-1)).clamp(-6.0, 6.0)
+    m = x.abs()
+    mag = ((m > 0.25).to(torch.uint8) + (m >= 0.75).to(torch.uint8)
+           + (m > 1.25).to(torch.uint8) + (m >= 1.75).to(torch.uint8)
+           + (m > 2.5).to(torch.uint8) + (m >= 3.5).to(torch.uint8)
+           + (m > 5.0).to(torch.uint8))
+    code = mag | (((x < 0) & (mag != 0)).to(torch.uint8) << 3)
+    code = code.view(*lead, Kp // 2, 2)
+    codes = code[..., 0] | (code[..., 1] << 4)
+    return codes.contiguous(), b.to(torch.uint8).contiguous()
+
+
+def dequantize_mxfp4(codes, scales):
+    """(codes [..., Kp/2], scales [..., Kp/32]) -> f32 [..., Kp], exact: a
+    grid value times a power of two."""
+    *lead, kb = codes.shape
+    grid = torch.tensor(E2M1_GRID + tuple(-v for v in E2M1_GRID),
+                        dtype=torch.float32, device=codes.device)
+    nib = torch.stack((codes & 0xf, codes >> 4), dim=-1).view(*lead, kb * 2)
+    val = grid[nib.long()]
+    # 2^(b-127) from the exponent field; b = 0 is the f32 subnormal 2^-127
+    b = scales.to(torch.int32)
+    sc = torch.where(b > 0, b << 23, torch.full_like(b, 0x00400000))
+    sc = sc.view(torch.float32)
+    return (val.view(*lead, kb // 16, 32) * sc.unsqueeze(-1)).view(
+        *lead, kb * 2)
+
+
+def mxfp4_linear(a_q, a_scale, codes, scales):
+    """Emulated e4m3 x MXFP4 GEMM: (a_q @ dequant(W)^T in fp32)
+    * a_scale[:, None] -> fp32 [rows, N]. The block scales act inside the sum
+    (as in the MFMA), the row scale after it (the kernel epilogue)."""
+    acc = a_q.float() @ dequantize_mxfp4(codes, scales).T
+    return acc * a_scale.unsqueeze(1)
+
+
+def grouped_gemm_mxfp4(out, a_q, a_scale, codes, scales, row_tok, tile_off,
+                       counts, max_tiles, gate_silu, bm: int = 64):
+    """Reference for grouped_gemm_mxfp4 (csrc/grouped_gemm_mxfp4.hip) and the
+    CPU path: the layout contract of `grouped_gemm_fp8` with MXFP4 weights —
+    e4m3 activation codes times exactly dequantised weights, products and
+    sums in fp32, the row scale after the sum, SwiGLU in fp32, then one
+    rounding to out's dtype. Padding rows of `out` are left untouched."""
+    E, N, _ = codes.shape
+    n_cols = N // 2 if gate_silu else N
+    for e in range(E):
+        c = int(counts[e])
+        if c == 0:
+            continue
+        s0 = int(tile_off[e]) * bm
+        if row_tok is not None:
+            idx = row_tok[s0:s0 + c].long().clamp(min=0)
+        else:
+            idx = torch.arange(s0, s0 + c, device=a_q.device)
+        rows = a_q.view(torch.uint8)[idx].view(torch.float8_e4m3fn)
+        y = mxfp4_linear(rows, a_scale[idx], codes[e], scales[e])
+        if gate_silu:
+            y = torch.nn.functional.silu(y[:, :n_cols]) * y[:, n_cols:]
+        out[s0:s0 + c] = y.to(out.dtype)
+    return out
+
+
 def apply_logit_penalties(logits, row_idx, hist, slot, hist_len, prompt_len,
                           rep, pres, freq, bias_tok, bias_val,
                           vocab_limit: int):
