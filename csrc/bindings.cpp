@@ -39,6 +39,8 @@ void sutro_attn_prefill(void*, const void*, const void*, const void*,
 void sutro_mfma32_probe(float*, const void*, const void*, hipStream_t);
 void sutro_gemm_tn_launch(void*, const void*, const void*, const void*, int,
                           int, long, int, int, int, int, hipStream_t);
+int sutro_gemm_tn_pipe_launch(void*, const void*, const void*, const void*,
+                              int, int, long, int, int, int, hipStream_t);
 void sutro_mfma16_probe(float*, const void*, const void*, hipStream_t);
 void sutro_hd64_stage_probe(float*, float*, void*, const void*, const void*,
                             const void*, int, float, hipStream_t);
@@ -207,6 +209,60 @@ torch::Tensor gemm_tn(torch::Tensor x, torch::Tensor w,
   sutro_gemm_tn_launch(out.data_ptr(), x.data_ptr(), w.data_ptr(), rp, (int)M,
                        (int)N, K, (int)bm, (int)bn, (int)swz, (int)xcd_swz,
                        cur_stream());
+  return out;
+}
+
+// gemm_tn on the 8-phase pipelined kernel (csrc/gemm_tn_pipe.hip): 256x256
+// tile, any M >= 1 and N >= 1 (edges clamped on load, guarded on store),
+// K%64==0. Bit-identical to gemm_tn at the same swz / xcd_swz.
+torch::Tensor gemm_tn_pipelined(torch::Tensor x, torch::Tensor w,
+                                c10::optional<torch::Tensor> res, long swz,
+                                long xcd_swz) {
+  CHECK_CUDA(x); CHECK_BF16(x); CHECK_CUDA(w); CHECK_BF16(w);
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2, "x and w must be 2-d");
+  TORCH_CHECK(x.is_contiguous() && w.is_contiguous(), "contiguous required");
+  const long M = x.size(0), K = x.size(1), N = w.size(0);
+  TORCH_CHECK(w.size(1) == K, "K mismatch");
+  TORCH_CHECK(M >= 1 && N >= 1 && K >= 64 && K % 64 == 0,
+              "shape not tile-divisible");
+  TORCH_CHECK(M < (1L << 31) && N < (1L << 31), "M/N too large");
+  TORCH_CHECK(swz >= 0 && swz <= 2, "swz must be 0, 1 or 2");
+  auto out = torch::empty({M, N}, x.options());
+  const void* rp = nullptr;
+  if (res.has_value()) {
+    CHECK_CUDA(*res); CHECK_BF16(*res);
+    TORCH_CHECK(res->is_contiguous() && res->dim() == 2 &&
+                res->size(0) == M && res->size(1) == N, "res shape");
+    rp = res->data_ptr();
+  }
+  const int e = sutro_gemm_tn_pipe_launch(
+      out.data_ptr(), x.data_ptr(), w.data_ptr(), rp, (int)M, (int)N, K,
+      rp ? 1 : 0, (int)swz, (int)xcd_swz, cur_stream());
+  TORCH_CHECK(e == 0, "gemm_tn_pipelined launch setup failed: ", e);
+  return out;
+}
+
+// out[M,I] = silu(x @ w[:I]^T) * (x @ w[I:]^T) on the merged gate_up weight
+// w [2I, K] (gate rows first), fused into the pipelined GEMM's epilogue.
+// Both products are rounded to bf16 before the activation, so the result
+// equals gemm_tn_pipelined followed by silu_mul bit for bit.
+torch::Tensor gemm_gate_up_silu(torch::Tensor x, torch::Tensor w, long swz,
+                                long xcd_swz) {
+  CHECK_CUDA(x); CHECK_BF16(x); CHECK_CUDA(w); CHECK_BF16(w);
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2, "x and w must be 2-d");
+  TORCH_CHECK(x.is_contiguous() && w.is_contiguous(), "contiguous required");
+  const long M = x.size(0), K = x.size(1), N = w.size(0);
+  TORCH_CHECK(w.size(1) == K, "K mismatch");
+  TORCH_CHECK(M >= 1 && K >= 64 && K % 64 == 0, "shape not tile-divisible");
+  TORCH_CHECK(N >= 256 && N % 256 == 0,
+              "gate_up rows must be 2*I with I % 128 == 0");
+  TORCH_CHECK(M < (1L << 31) && N < (1L << 31), "M/N too large");
+  TORCH_CHECK(swz >= 0 && swz <= 2, "swz must be 0, 1 or 2");
+  auto out = torch::empty({M, N / 2}, x.options());
+  const int e = sutro_gemm_tn_pipe_launch(
+      out.data_ptr(), x.data_ptr(), w.data_ptr(), nullptr, (int)M, (int)N, K,
+      2, (int)swz, (int)xcd_swz, cur_stream());
+  TORCH_CHECK(e == 0, "gemm_gate_up_silu launch setup failed: ", e);
   return out;
 }
 
@@ -571,4 +627,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("w"), py::arg("res") = c10::nullopt,
         py::arg("bm") = 256, py::arg("bn") = 256, py::arg("swz") = 2,
         py::arg("xcd_swz") = 0);
+  m.def("gemm_tn_pipelined", &gemm_tn_pipelined,
+        "bf16 TN GEMM (MFMA, 8-phase glds pipeline, any M/N)",
+        py::arg("x"), py::arg("w"), py::arg("res") = c10::nullopt,
+        py::arg("swz") = 2, py::arg("xcd_swz") = 1);
+  m.def("gemm_gate_up_silu", &gemm_gate_up_silu,
+        "SwiGLU fused into the pipelined gate_up GEMM",
+        py::arg("x"), py::arg("w"), py::arg("swz") = 2,
+        py::arg("xcd_swz") = 1);
 }

@@ -21,6 +21,7 @@ SOURCES = [
     "csrc/attn_decode_mfma.hip",
     "csrc/attn_prefill.hip",
     "csrc/gemm_tn.hip",
+    "csrc/gemm_tn_pipe.hip",
     "csrc/sampler.hip",
     "csrc/grouped_gemm.hip",
     "csrc/grouped_gemm_fp8.hip",

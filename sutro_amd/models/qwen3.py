@@ -2,8 +2,10 @@
 
 One architecture covers the whole registry: RMSNorm + RoPE-NeoX + GQA paged
 attention + SwiGLU MLP (dense) or top-k routed SwiGLU experts (MoE).
-GEMMs go through F.linear (hipBLASLt on ROCm); everything between GEMMs is a
-hand-written HIP kernel on GPU (see sutro_amd/ops).
+GEMMs go through F.linear (hipBLASLt on ROCm), except the dense MLP's gate_up
+projection where ops.gate_up_silu routes it to the fused GEMM + SwiGLU kernel;
+everything between GEMMs is a hand-written HIP kernel on GPU (see
+sutro_amd/ops).
 """
 
 from __future__ import annotations
@@ -123,7 +125,8 @@ class Qwen3MLP(nn.Module):
         _mark_shard(self.down_proj.weight, (hidden, intermediate), 1, tp)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        return self.tp.all_reduce(self.down_proj(ops.silu_mul(self.gate_up_proj(x))))
+        act = ops.gate_up_silu(x, self.gate_up_proj.weight)
+        return self.tp.all_reduce(self.down_proj(act))
 
 
 class Qwen3MoE(nn.Module):

@@ -70,6 +70,64 @@ def silu_mul(x: torch.Tensor) -> torch.Tensor:
     return torch_ref.silu_mul(x)
 
 
+# Dense-MLP gate_up routing: (K, 2I) -> (min_M, held_back). The fused kernel
+# (csrc/gemm_tn_pipe.hip, SwiGLU epilogue) runs for every token count
+# M >= min_M, the smallest M from which every measured point beat the library
+# GEMM + silu_mul pair by the margin of profiles/PROFILES.md capture G1;
+# shapes not listed were not measured to win and stay on the library pair.
+# held_back: hipGraph decode buckets kept on the library pair although they
+# clear the margin. The fused kernel sums K in gemm_tn's order, which is also
+# the order of the library kernels picked at the other buckets (identical
+# results there, G1); at these three the library's kernel sums a few tiles
+# differently, and a decode batch that shrinks through them would no longer
+# return what the library path returns.
+GATE_UP_FUSED_RULE: dict = {
+    (5120, 51200): (1152, frozenset({1536, 1664, 1792})),   # Qwen3-32B
+}
+
+# SUTRO_GATE_UP_FUSED=1 forces the fused kernel wherever the shape qualifies,
+# =0 forces the library pair (A/B only); unset follows GATE_UP_FUSED_RULE.
+_GATE_UP_FORCE: Optional[bool] = {"1": True, "0": False}.get(
+    os.environ.get("SUTRO_GATE_UP_FUSED", ""))
+
+
+def set_gate_up_fused(mode: Optional[bool]) -> None:
+    """In-process form of SUTRO_GATE_UP_FUSED: True / False force the path,
+    None restores the measured rule."""
+    global _GATE_UP_FORCE
+    _GATE_UP_FORCE = mode
+
+
+def gate_up_silu_qualifies(x: torch.Tensor, weight: torch.Tensor) -> bool:
+    """Shapes the fused kernel takes: bf16, contiguous, K % 64 == 0 and
+    I % 128 == 0 (weight is the merged [2I, K], gate rows first)."""
+    return (x.dim() == 2 and weight.dim() == 2 and x.shape[0] >= 1
+            and x.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16
+            and x.is_contiguous() and weight.is_contiguous()
+            and x.shape[1] == weight.shape[1] and x.shape[1] % 64 == 0
+            and weight.shape[0] >= 256 and weight.shape[0] % 256 == 0)
+
+
+def gate_up_silu(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    """SwiGLU of the merged gate_up projection: silu(x Wg^T) * (x Wu^T) for
+    weight = [Wg; Wu] of shape [2I, K]; returns [T, I]. On GPU, qualifying
+    shapes selected by the routing rule run as ONE kernel (no [T, 2I]
+    intermediate, no silu_mul pass); everything else is the library GEMM
+    followed by silu_mul. No host sync, output from the caching allocator:
+    safe under hipGraph capture."""
+    if _use_hip(x) and gate_up_silu_qualifies(x, weight):
+        if _GATE_UP_FORCE is None:
+            min_m, held_back = GATE_UP_FUSED_RULE.get(
+                (x.shape[1], weight.shape[0]), (None, ()))
+            fused = (min_m is not None and x.shape[0] >= min_m
+                     and x.shape[0] not in held_back)
+        else:
+            fused = _GATE_UP_FORCE
+        if fused:
+            return _require_hip().gemm_gate_up_silu(x, weight)
+    return silu_mul(torch.nn.functional.linear(x, weight))
+
+
 def fused_qkv_prep(
     qkv: torch.Tensor,            # [T, Hq*D + 2*Hk*D] (qkv GEMM output)
     num_heads: int, num_kv_heads: int, head_dim: int,
