@@ -376,7 +376,7 @@ extern "C" void sutro_attn_decode(void* out, const void* q, const void* k_cache,
   // (bf16: 10654 vs 10134 tok/s at batch 1024 / ctx 128; attention slope
   // halves at ctx 512; fp8 dequants with the native pk converts at the K/V
   // fragment loads). head_dim 64 routes to MFMA too since the DB-bounded
-  // alpha-rescale fix (attn_decode_mfma.hip:202) — verified against the fp32
+  // alpha-rescale fix (attn_decode_mfma.h, mfma_page_update) — verified against the fp32
   // reference by test_attn_head_dim_64 on hardware.
   // SUTRO_DECODE_VALU=1 falls back to the VALU kernel for A/B.
   if ((head_dim == 128 || head_dim == 64) && Hq / Hk <= 8 &&

@@ -18,35 +18,8 @@
 //   A[16,32]: lane l holds A[l%16][(l/16)*8 + j], j=0..7
 //   B[32,16]: lane l holds B[(l/16)*8 + j][l%16]
 //   C/D     : lane l holds D[(l/16)*4 + r][l%16], r=0..3 (guide §3)
-#include "common.h"
+#include "attn_decode_mfma.h"
 #include <cstdlib>
-
-#define BS 32
-#define MAXG 8
-#define QT_PAD_B 256 // Qt row bytes (128 bf16)
-#define PV_PAD 40    // padded row length (elems) for P and Vt tiles
-
-typedef s16x8 bf16frag;
-typedef float f32x4_ __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f32x4 mfma16(bf16frag a, bf16frag b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
-// 8 consecutive KV elements at byte pointer p -> bf16 fragment.
-// bf16 cache: one 16B load. e4m3 cache: 8B load + native pk converts.
-template <bool KV8>
-__device__ __forceinline__ bf16frag load_kv_frag(const u8* p) {
-  if constexpr (!KV8) return *(const s16x8*)p;
-  const u32x2 raw = *(const u32x2*)p;
-  float f[8];
-  fp8x4_to_f32(raw[0], f);
-  fp8x4_to_f32(raw[1], f + 4);
-  bf16frag r;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) r[j] = (short)f2bf(f[j]);
-  return r;
-}
 
 template <int D>
 struct MfmaSmem {
@@ -57,14 +30,10 @@ struct MfmaSmem {
   float linv[16];
 };
 
-// row-local XOR swizzle; mask keeps the offset inside the 2*D-byte row
-template <int D>
-__device__ __forceinline__ int qt_swz(int head, int byte_in_row) {
-  constexpr int mask = (D == 128) ? 15 : 7;
-  return head * (2 * D) + (byte_in_row ^ ((head & mask) << 4));
-}
-
-template <int D, bool KV8>
+// CONT (shared-prefix decode, attn_decode_prefix.hip): a row with
+// row_prefix_pages[row] = P > 0 resumes from the f32 softmax state the
+// partial kernel left for its first P pages and starts its page loop at P.
+template <int D, bool KV8, bool CONT = false>
 __global__ __launch_bounds__(256) void attn_decode_mfma_kernel(
     u16* __restrict__ out,            // [n_dec, Hq, D]
     const u16* __restrict__ q,        // [n_dec, Hq, D]
@@ -72,7 +41,11 @@ __global__ __launch_bounds__(256) void attn_decode_mfma_kernel(
     const u8* __restrict__ v_cache,
     const int* __restrict__ block_tables,  // [S, bt_stride]
     const int* __restrict__ seq_lens,      // [S]
-    int bt_stride, int n_dec, int Hq, int Hk, int seq_offset, float scale) {
+    int bt_stride, int n_dec, int Hq, int Hk, int seq_offset, float scale,
+    const int* __restrict__ row_prefix_pages = nullptr,  // [n_dec] (CONT)
+    const float* __restrict__ part_o = nullptr,          // [n_dec, Hq, D]
+    const float* __restrict__ part_m = nullptr,          // [n_dec, Hq]
+    const float* __restrict__ part_l = nullptr) {
   const int lane = threadIdx.x & (WAVE - 1);
   const int wid = threadIdx.x / WAVE;
   const long item = (long)blockIdx.x * (blockDim.x / WAVE) + wid;
@@ -108,115 +81,49 @@ __global__ __launch_bounds__(256) void attn_decode_mfma_kernel(
     }
   }
 
+  wave_lds_sync();
+
   float m_run = -1e30f, l_run = 0.f;   // for head lo16
   constexpr int DB = D / 16;           // d-blocks
   f32x4 acc[DB];                       // O[head hi4*4+r][d lo16 + 16*dblk]
 #pragma unroll
   for (int b = 0; b < DB; ++b) acc[b] = (f32x4)(0.f);
 
-  constexpr int ES = KV8 ? 1 : 2;  // bytes per cache element
-  for (int pg = 0; pg < npages; ++pg) {
-    const long kv_base = (((long)bt[pg] * Hk + kh) * BS) * D * ES;
-    const int valid = min(BS, L - pg * BS);
-
-    // ---- stage V^T (d-major) while issuing K fragment loads
-    // lane l covers V rows pos = l%32? use: each lane moves 2 chunks of 8
-    // elems: item = lane*2+c -> pos = item/16? Simpler: 64 lanes x 8 iters of
-    // 8 elems = 4096 elems = the page.
-    {
-      const u8* vsrc = v_cache + kv_base;
-#pragma unroll
-      for (int it = 0; it < (BS * D) / ((int)WAVE * 8); ++it) {
-        const int flat = it * (int)WAVE + lane;   // 8-elem chunk id
-        const int pos = flat & 31;                // pos-major across lanes:
-        const int d0 = (flat >> 5) * 8;           // scatter writes spread banks
-        const bf16frag vx = load_kv_frag<KV8>(vsrc + (pos * D + d0) * ES);
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          sm->vt[(d0 + j) * PV_PAD + pos] = (u16)vx[j];
+  int pg0 = 0;
+  if constexpr (CONT) {
+    pg0 = min(row_prefix_pages[sd], npages);
+    if (pg0 > 0) {
+      const long hrow = (long)sd * Hq + kh * G;
+      if (lo16 < G) {
+        m_run = part_m[hrow + lo16];
+        l_run = part_l[hrow + lo16];
       }
-    }
-
-    // ---- QK^T via MFMA: two 16-position halves
-    f32x4 s01[2];
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-      f32x4 d = (f32x4)(0.f);
-#pragma unroll
-      for (int kk = 0; kk < D / 32; ++kk) {
-        // A = K frag: row pos = half*16 + l%16, dims kk*32 + (l/16)*8..+8
-        const u8* krow = k_cache + kv_base +
-                         ((long)(half * 16 + lo16) * D + kk * 32 + hi4 * 8) *
-                             ES;
-        bf16frag ka = load_kv_frag<KV8>(krow);
-        // B = Qt frag: B[k][head]: lane reads qt[head l%16][kk*32+(l/16)*8]
-        bf16frag qb = *(const s16x8*)((char*)sm->qt +
-                                      qt_swz<D>(lo16, (kk * 32 + hi4 * 8) * 2));
-        d = mfma16(ka, qb, d);
-      }
-      s01[half] = d;
-    }
-
-    // ---- online softmax: lane owns head lo16; 8 scores (2 halves x 4 r)
-    float sv[8];
-#pragma unroll
-    for (int half = 0; half < 2; ++half)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int pos = half * 16 + hi4 * 4 + r;
-        float x = s01[half][r];
-        if (pos >= valid) x = -1e30f;
-        sv[half * 4 + r] = x;
+        const int head = hi4 * 4 + r;
+        if (head >= G) continue;
+#pragma unroll
+        for (int b = 0; b < DB; ++b)
+          acc[b][r] = part_o[(hrow + head) * D + b * 16 + lo16];
       }
-    float tmax = sv[0];
-#pragma unroll
-    for (int i = 1; i < 8; ++i) tmax = fmaxf(tmax, sv[i]);
-    tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
-    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-    const float m_new = fmaxf(m_run, tmax);
-    const float al = __expf(m_run - m_new);
-    m_run = m_new;
-    float psum = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      sv[i] = __expf(sv[i] - m_new);
-      psum += sv[i];
     }
-    psum += __shfl_xor(psum, 16, 64);
-    psum += __shfl_xor(psum, 32, 64);
-    l_run = l_run * al + psum;
-    if (hi4 == 0) sm->alpha[lo16] = al;
-    // write P[head][pos] (bf16)
-#pragma unroll
-    for (int half = 0; half < 2; ++half)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        sm->p[lo16 * PV_PAD + half * 16 + hi4 * 4 + r] =
-            f2bf(sv[half * 4 + r]);
+  }
 
-    // ---- rescale O by alpha of the row's head ((l/16)*4+r)
-    float alr[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) alr[r] = sm->alpha[hi4 * 4 + r];
-#pragma unroll
-    for (int b = 0; b < DB; ++b)   // NOT 8: at head_dim 64 acc has DB=4
-#pragma unroll                     // entries — the out-of-bounds writes here
-      for (int r = 0; r < 4; ++r)  // poisoned the whole accumulator chain
-        acc[b][r] *= alr[r];       // (ROADMAP.md: D=64 post-mortem)
-
-    // ---- PV via MFMA: A = P[head16, pos32], B = Vt-read V[pos32, d16]
-    bf16frag pa = *(const s16x8*)(sm->p + lo16 * PV_PAD + hi4 * 8);
-#pragma unroll
-    for (int b = 0; b < DB; ++b) {
-      // B frag: V[pos=(l/16)*8+j][d = b*16 + l%16] from vt[d][pos]
-      bf16frag vb = *(const s16x8*)(sm->vt + (b * 16 + lo16) * PV_PAD +
-                                    hi4 * 8);
-      acc[b] = mfma16(pa, vb, acc[b]);
-    }
+  constexpr int ES = KV8 ? 1 : 2;  // bytes per cache element
+  for (int pg = pg0; pg < npages; ++pg) {
+    const long kv_base = (((long)bt[pg] * Hk + kh) * BS) * D * ES;
+    const int valid = min(BS, L - pg * BS);
+    // stage V^T (d-major) while the K fragment loads are in flight
+    mfma_stage_vt<D, KV8>(sm->vt, v_cache + kv_base, lane);
+    bf16frag ka[2][D / 32];
+    mfma_load_k<D, KV8>(ka, k_cache + kv_base, lo16, hi4);
+    mfma_page_update<D>(sm->qt, sm->vt, sm->p, sm->alpha, ka, valid, lo16,
+                        hi4, m_run, l_run, acc);
   }
 
   // ---- epilogue: divide rows by their head's l and scatter
   if (hi4 == 0) sm->linv[lo16] = 1.0f / l_run;
+  wave_lds_sync();
   float li[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) li[r] = sm->linv[hi4 * 4 + r];
@@ -230,6 +137,39 @@ __global__ __launch_bounds__(256) void attn_decode_mfma_kernel(
   }
 }
 
+// CONT: the shared-prefix route passes the partial-state buffers
+template <bool CONT>
+static void launch_decode_mfma(void* out, const void* q, const void* k_cache,
+                               const void* v_cache, const int* block_tables,
+                               const int* seq_lens, int bt_stride, int n_dec,
+                               int Hq, int Hk, int seq_offset, float scale,
+                               int kv_fp8, int head_dim,
+                               const int* row_prefix_pages,
+                               const float* part_o, const float* part_m,
+                               const float* part_l, hipStream_t s) {
+  // 2 waves/block (bf16 D=128: 31.4 KB LDS -> 5 blocks/CU)
+  static const char* wpb_env = getenv("SUTRO_DECODE_WPB");
+  const int wpb = wpb_env ? atoi(wpb_env) : 2;
+  const long items = (long)n_dec * Hk;
+  const long blocks = (items + wpb - 1) / wpb;
+#define LAUNCH_MFMA(D, KV8)                                                  \
+  if (head_dim == D && kv_fp8 == (KV8 ? 1 : 0)) {                            \
+    hipLaunchKernelGGL((attn_decode_mfma_kernel<D, KV8, CONT>),              \
+                       dim3((unsigned)blocks), dim3(wpb * WAVE),             \
+                       sizeof(MfmaSmem<D>) * wpb, s, (u16*)out,              \
+                       (const u16*)q, (const u8*)k_cache,                    \
+                       (const u8*)v_cache, block_tables, seq_lens,           \
+                       bt_stride, n_dec, Hq, Hk, seq_offset, scale,          \
+                       row_prefix_pages, part_o, part_m, part_l);            \
+    return;                                                                  \
+  }
+  LAUNCH_MFMA(128, false)
+  LAUNCH_MFMA(128, true)
+  LAUNCH_MFMA(64, false)
+  LAUNCH_MFMA(64, true)
+#undef LAUNCH_MFMA
+}
+
 extern "C" void sutro_attn_decode_mfma(void* out, const void* q,
                                        const void* k_cache,
                                        const void* v_cache,
@@ -238,26 +178,24 @@ extern "C" void sutro_attn_decode_mfma(void* out, const void* q,
                                        int n_dec, int Hq, int Hk,
                                        int seq_offset, float scale, int kv_fp8,
                                        int head_dim, hipStream_t s) {
-  // 2 waves/block (bf16 D=128: 31.4 KB LDS -> 5 blocks/CU)
-  static const char* wpb_env = getenv("SUTRO_DECODE_WPB");
-  const int wpb = wpb_env ? atoi(wpb_env) : 2;
-  const long items = (long)n_dec * Hk;
-  const long blocks = (items + wpb - 1) / wpb;
-#define LAUNCH_MFMA(D, KV8)                                                  \
-  if (head_dim == D && kv_fp8 == (KV8 ? 1 : 0)) {                            \
-    hipLaunchKernelGGL((attn_decode_mfma_kernel<D, KV8>),                    \
-                       dim3((unsigned)blocks), dim3(wpb * WAVE),             \
-                       sizeof(MfmaSmem<D>) * wpb, s, (u16*)out,              \
-                       (const u16*)q, (const u8*)k_cache,                    \
-                       (const u8*)v_cache, block_tables, seq_lens,           \
-                       bt_stride, n_dec, Hq, Hk, seq_offset, scale);         \
-    return;                                                                  \
-  }
-  LAUNCH_MFMA(128, false)
-  LAUNCH_MFMA(128, true)
-  LAUNCH_MFMA(64, false)
-  LAUNCH_MFMA(64, true)
-#undef LAUNCH_MFMA
+  launch_decode_mfma<false>(out, q, k_cache, v_cache, block_tables, seq_lens,
+                            bt_stride, n_dec, Hq, Hk, seq_offset, scale,
+                            kv_fp8, head_dim, nullptr, nullptr, nullptr,
+                            nullptr, s);
+}
+
+// per-row kernel resuming from the partial kernel's state (decode-only batch:
+// row i of every buffer is sequence i)
+extern "C" void sutro_attn_decode_mfma_cont(
+    void* out, const void* q, const void* k_cache, const void* v_cache,
+    const int* block_tables, const int* seq_lens, int bt_stride, int n_dec,
+    int Hq, int Hk, float scale, int kv_fp8, int head_dim,
+    const int* row_prefix_pages, const float* part_o, const float* part_m,
+    const float* part_l, hipStream_t s) {
+  launch_decode_mfma<true>(out, q, k_cache, v_cache, block_tables, seq_lens,
+                           bt_stride, n_dec, Hq, Hk, 0, scale, kv_fp8,
+                           head_dim, row_prefix_pages, part_o, part_m, part_l,
+                           s);
 }
 
 // ---- debug probe: run the D=64 decode stages for one (seq, kv_head) and

@@ -36,6 +36,11 @@ void sutro_attn_prefill(void*, const void*, const void*, const void*,
                         const int*, const int*, const int*, const int*,
                         const int*, int, int, int, int, int, int, float,
                         hipStream_t);
+void sutro_attn_decode_shared(void*, const void*, const void*, const void*,
+                              const int*, const int*, int, int, int, int,
+                              float, int, int, const int*, const int*, int,
+                              int, float*, float*, float*, hipStream_t);
+int sutro_attn_prefix_tile_rows(int, int);
 void sutro_mfma32_probe(float*, const void*, const void*, hipStream_t);
 void sutro_gemm_tn_launch(void*, const void*, const void*, const void*, int,
                           int, long, int, int, int, int, hipStream_t);
@@ -162,6 +167,52 @@ void paged_attention(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
                       is_fp8(k_cache) ? 1 : 0, seq_offset, (float)scale,
                       cur_stream());
   }
+}
+
+// decode-only paged attention with shared-prefix tiles (attn_decode_prefix.hip)
+void paged_attention_decode_shared(
+    torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
+    torch::Tensor v_cache, torch::Tensor block_tables, torch::Tensor seq_lens,
+    double scale, torch::Tensor row_prefix_pages, torch::Tensor tile_rows,
+    torch::Tensor part_o, torch::Tensor part_m, torch::Tensor part_l) {
+  CHECK_CUDA(q); CHECK_CONTIG(q); CHECK_BF16(q); CHECK_CONTIG(k_cache);
+  CHECK_CONTIG(out); CHECK_CONTIG(v_cache); CHECK_CONTIG(block_tables);
+  CHECK_CONTIG(row_prefix_pages); CHECK_CONTIG(tile_rows);
+  CHECK_CONTIG(part_o); CHECK_CONTIG(part_m); CHECK_CONTIG(part_l);
+  const int n = q.size(0), Hq = q.size(1), D = q.size(2);
+  const int Hk = k_cache.size(1);
+  TORCH_CHECK(D == 128 || D == 64,
+              "shared-prefix decode supports head_dim 64/128 (got ", D, ")");
+  TORCH_CHECK(k_cache.size(2) == 32, "attention kernels require kv_block_size 32");
+  TORCH_CHECK(Hq % Hk == 0 && Hq / Hk <= 8,
+              "GQA group size must divide and be <= 8");
+  TORCH_CHECK(block_tables.scalar_type() == at::kInt &&
+              seq_lens.scalar_type() == at::kInt &&
+              row_prefix_pages.scalar_type() == at::kInt &&
+              tile_rows.scalar_type() == at::kInt, "index tensors must be int32");
+  TORCH_CHECK(block_tables.size(0) >= n && seq_lens.numel() >= n &&
+              row_prefix_pages.numel() >= n, "per-row tensors shorter than q");
+  TORCH_CHECK(tile_rows.dim() == 2 &&
+              tile_rows.size(1) == sutro_attn_prefix_tile_rows(Hq, Hk),
+              "tile_rows must be [NT, ", sutro_attn_prefix_tile_rows(Hq, Hk), "]");
+  TORCH_CHECK(part_o.scalar_type() == at::kFloat &&
+              part_m.scalar_type() == at::kFloat &&
+              part_l.scalar_type() == at::kFloat, "partial buffers must be f32");
+  TORCH_CHECK(part_o.numel() >= (int64_t)n * Hq * D &&
+              part_m.numel() >= (int64_t)n * Hq &&
+              part_l.numel() >= (int64_t)n * Hq, "partial buffers too small");
+  sutro_attn_decode_shared(
+      out.data_ptr(), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+      block_tables.data_ptr<int>(), seq_lens.data_ptr<int>(),
+      (int)block_tables.size(1), n, Hq, Hk, (float)scale,
+      is_fp8(k_cache) ? 1 : 0, D, row_prefix_pages.data_ptr<int>(),
+      tile_rows.data_ptr<int>(), (int)tile_rows.size(0),
+      (int)tile_rows.size(1), part_o.data_ptr<float>(),
+      part_m.data_ptr<float>(), part_l.data_ptr<float>(), cur_stream());
+}
+
+int64_t prefix_tile_rows(int64_t Hq, int64_t Hk) {
+  return sutro_attn_prefix_tile_rows((int)Hq, (int)Hk);
 }
 
 void qkv_prep(torch::Tensor qkv, torch::Tensor q_out, torch::Tensor k_cache,
@@ -604,6 +655,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("qkv_prep", &qkv_prep, "fused qk-norm + RoPE + KV write + q gather");
   m.def("mean_pool_normalize", &mean_pool_normalize, "varlen mean pool + L2");
   m.def("paged_attention", &paged_attention, "paged prefill+decode attention");
+  m.def("paged_attention_decode_shared", &paged_attention_decode_shared,
+        "decode attention, shared-prefix tiles + per-row continuation");
+  m.def("prefix_tile_rows", &prefix_tile_rows,
+        "rows per shared-prefix tile for a (Hq, Hk) head layout");
   m.def("mfma32_probe", &mfma32_probe, "MFMA fragment-layout probe");
   m.def("mfma16_probe", &mfma16_probe, "16x16 MFMA fragment-layout probe");
   m.def("hd64_stage_probe", &hd64_stage_probe, "D=64 decode stage dump probe");

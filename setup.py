@@ -19,6 +19,7 @@ SOURCES = [
     "csrc/pool.hip",
     "csrc/attn_decode.hip",
     "csrc/attn_decode_mfma.hip",
+    "csrc/attn_decode_prefix.hip",
     "csrc/attn_prefill.hip",
     "csrc/gemm_tn.hip",
     "csrc/gemm_tn_pipe.hip",

@@ -45,3 +45,9 @@ class ForwardBatch:
     tile_seq: Optional[torch.Tensor] = None   # [n_tiles] int32 seq index
     tile_q0: Optional[torch.Tensor] = None    # [n_tiles] int32 local row start
     prefill_token_count: int = 0              # flat rows belonging to prefills
+    # shared-prefix decode (decode-only batches; None = ordinary attention):
+    # leading pages of each row covered by its tile, the tiles' row indices
+    # (-1 = empty slot), and the f32 partial-state scratch (o, m, l)
+    row_prefix_pages: Optional[torch.Tensor] = None   # [S] int32
+    prefix_tile_rows: Optional[torch.Tensor] = None   # [NT, R] int32
+    prefix_partials: Optional[tuple] = None

@@ -66,8 +66,26 @@ class EngineConfig:
     # "mxfp4": OCP MX e2m1 codes with one e8m0 scale per 32 K-elements (4.25
     # bits per weight), dequantised inside the block-scaled MFMA (W4A8).
     moe_weight_dtype: str = "bf16"
+    # block-hash prefix cache: full blocks of computed prompt tokens are
+    # indexed by (parent block, token ids) and shared between rows by
+    # reference count, so a job's common system prompt is prefilled and held
+    # once (docs/ENGINE.md, "Prefix cache"). Forced off for embedding specs
+    # (mean pooling needs every token's hidden state).
+    enable_prefix_caching: bool = False
+    # decode attention over shared prefix pages: "per_row" streams them once
+    # per row (the ordinary kernel); "shared" streams them once per tile of
+    # rows with a common prefix and hands the f32 softmax state to the
+    # per-row kernel for the rest — bit-identical output. Meaningful only
+    # with enable_prefix_caching on the GPU MFMA decode route.
+    prefix_decode: str = "per_row"
 
     def __post_init__(self) -> None:
+        if self.prefix_decode not in ("per_row", "shared"):
+            raise ValueError(
+                f"prefix_decode must be 'per_row' or 'shared', "
+                f"got {self.prefix_decode!r}")
+        if self.spec.embedding:
+            self.enable_prefix_caching = False
         if self.moe_weight_dtype not in ("bf16", "fp8_e4m3", "mxfp4"):
             raise ValueError(
                 f"moe_weight_dtype must be 'bf16', 'fp8_e4m3' or 'mxfp4', "

@@ -40,6 +40,7 @@ class StepStats:
     scheduled_tokens: int = 0
     prefill_tokens: int = 0
     output_tokens: int = 0
+    prefix_hit_tokens: int = 0   # prompt tokens served from the prefix cache
     finished: List[Request] = field(default_factory=list)
 
 
@@ -133,6 +134,7 @@ class LLMEngine:
             head_dim=self.spec.head_dim,
             dtype=cfg.kv_torch_dtype(),
             device=cfg.device,
+            prefix_caching=cfg.enable_prefix_caching,
         )
         # block 0 is reserved scratch: hipGraph padding rows read/write it
         self.scratch_block = self.kv.allocator.allocate(1)[0]
@@ -157,6 +159,29 @@ class LLMEngine:
                     mod.prealloc_workspace(max(cfg.max_tokens_per_step,
                                                cfg.max_num_seqs))
                     break  # workspace is shared across layers
+
+        # shared-prefix decode attention: only with the prefix cache, on the
+        # GPU, where the MFMA decode route runs; "shared" anywhere else is
+        # the ordinary path
+        self.prefix_shared = False
+        self.prefix_tile_steps = 0   # decode steps that ran a non-empty tile
+        self._prefix_partials = None
+        if (cfg.prefix_decode == "shared" and cfg.enable_prefix_caching
+                and cfg.device.startswith("cuda")):
+            from .. import ops
+
+            hq, hk = self.local_heads()
+            if ops.shared_decode_supported(self.spec.head_dim, hq, hk,
+                                           cfg.kv_block_size):
+                self.prefix_shared = True
+            else:
+                import warnings
+
+                warnings.warn(
+                    f"prefix_decode='shared' needs head_dim 64/128, a GQA "
+                    f"group <= 8 and kv_block_size 32 (got head_dim "
+                    f"{self.spec.head_dim}, {hq}/{hk} heads, block "
+                    f"{cfg.kv_block_size}); running 'per_row'")
 
         self.graph_runner = None
         if (cfg.device.startswith("cuda") and not cfg.enforce_eager
@@ -252,6 +277,12 @@ class LLMEngine:
     def abort_request(self, req: Request) -> None:
         self.scheduler.abort_request(req)
 
+    def local_heads(self) -> tuple:
+        """(query heads, kv heads) of this rank's attention shards."""
+        tp = max(1, self.cfg.tp_size)
+        return (self.spec.num_heads // tp,
+                max(1, self.spec.num_kv_heads // tp))
+
     def has_work(self) -> bool:
         return self.scheduler.has_work()
 
@@ -307,8 +338,13 @@ class LLMEngine:
                 tiles_q0.append(j)
         prefill_token_count = int(qlocs[sb.num_prefills])
 
+        prefix_kw = {}
+        if self.prefix_shared and sb.num_prefills == 0 and S > 0:
+            prefix_kw = self._prefix_tiles_eager(sb, block_tables, seq_lens)
+
         dev = self.device
         return ForwardBatch(
+            **prefix_kw,
             input_ids=torch.from_numpy(input_ids).to(dev),
             positions=torch.from_numpy(positions).to(dev),
             slot_mapping=torch.from_numpy(slots).to(dev),
@@ -323,6 +359,36 @@ class LLMEngine:
             tile_q0=torch.tensor(tiles_q0, dtype=torch.int32, device=dev),
             prefill_token_count=prefill_token_count,
         )
+
+    def _prefix_tiles_eager(self, sb: ScheduledBatch, block_tables: np.ndarray,
+                            seq_lens: np.ndarray) -> dict:
+        """Shared-prefix tiles for a decode-only batch run without a graph
+        (the graph runner fills its static copies in `_fill_host`)."""
+        from .. import ops
+        from .prefix_groups import fill_prefix_tiles, max_tiles
+
+        S = len(sb.reqs)
+        hq, hk = self.local_heads()
+        R = ops.prefix_tile_rows(hq, hk)
+        tile_rows = np.empty((max_tiles(S, R), R), dtype=np.int32)
+        row_pages = np.empty(S, dtype=np.int32)
+        pb = self.kv.prefix_blocks
+        nb = np.fromiter((pb.get(r.req_id, 0) for r in sb.reqs), np.int64, S)
+        used = fill_prefix_tiles(tile_rows, row_pages, block_tables, seq_lens,
+                                 S, nb, self.kv.allocator.ref,
+                                 self.kv.block_size)
+        # the kernel's precondition: a position beyond every row's prefix
+        assert (seq_lens > row_pages.astype(np.int64) * self.kv.block_size).all()
+        if used:
+            self.prefix_tile_steps += 1
+        if self._prefix_partials is None:
+            self._prefix_partials = ops.alloc_prefix_partials(
+                self.cfg.max_num_seqs, hq, self.spec.head_dim, self.device)
+        dev = self.device
+        return dict(
+            row_prefix_pages=torch.from_numpy(row_pages).to(dev),
+            prefix_tile_rows=torch.from_numpy(tile_rows).to(dev),
+            prefix_partials=tuple(t[:S] for t in self._prefix_partials))
 
     def _sampling_reqs(self, sb: ScheduledBatch) -> List[Request]:
         out = []
@@ -375,10 +441,22 @@ class LLMEngine:
             num_new_tokens=[c for _, c in kept],
             num_prefills=sum(1 for r, _ in kept if r.in_prefill))
 
+    @property
+    def prefix_query_tokens(self) -> int:
+        """Prompt tokens of all admissions with the prefix cache on."""
+        return self.scheduler.prefix_query_tokens
+
+    @property
+    def prefix_hit_tokens(self) -> int:
+        """Of those, tokens whose KV came from the prefix cache."""
+        return self.scheduler.prefix_hit_tokens
+
     @torch.no_grad()
     def step(self) -> StepStats:
+        hits0 = self.scheduler.prefix_hit_tokens
         sb = self.scheduler.schedule()
         stats = StepStats()
+        stats.prefix_hit_tokens = self.scheduler.prefix_hit_tokens - hits0
         if not sb.reqs:
             # drain the final lagged tokens (finished-row extras only)
             self._consume_pending(stats)
@@ -432,7 +510,8 @@ class LLMEngine:
                            [r.alloc_gen for r in sub.reqs])
             self._consume_pending(stats)  # previous step's tokens (lagged)
             self._pending_decode = new_pending
-            self.total_prompt_tokens += stats.prefill_tokens
+            self.total_prompt_tokens += (stats.prefill_tokens
+                                         + stats.prefix_hit_tokens)
             self.total_output_tokens += stats.output_tokens
             return stats
 
@@ -481,13 +560,21 @@ class LLMEngine:
                 self._apply_sampled(req, int(tok), float(lp), stats)
             stats.prefill_tokens += sum(sub.num_new_tokens[: sub.num_prefills])
 
-        self.total_prompt_tokens += stats.prefill_tokens
+        # cache hits count as submitted prompt tokens (job accounting is the
+        # same with the prefix cache on or off)
+        self.total_prompt_tokens += stats.prefill_tokens + stats.prefix_hit_tokens
         self.total_output_tokens += stats.output_tokens
         return stats
 
     def _advance_computed(self, sb: ScheduledBatch) -> None:
         for req, c in zip(sb.reqs, sb.num_new_tokens):
             req.num_computed_tokens += c
+        if self.kv.prefix_caching and sb.num_prefills:
+            # the step that computed these blocks is behind us (on the
+            # stream): from now on they are matchable and never written
+            for req in sb.reqs[: sb.num_prefills]:
+                self.kv.register_computed(req.req_id, req.prompt_token_ids,
+                                          req.num_computed_tokens)
 
     def _fsm_masks(self, reqs: List[Request], device) -> Optional[torch.Tensor]:
         """Packed FSM mask rows [n, W] int32 (guided.py layout), or None when

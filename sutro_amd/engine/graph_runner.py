@@ -18,9 +18,14 @@ import numpy as np
 import torch
 
 from .batch import ForwardBatch, ScheduledBatch
+from .prefix_groups import fill_prefix_tiles, max_tiles
 
 
 class DecodeGraphRunner:
+    # shared-prefix decode state (class defaults: the ordinary path)
+    prefix_shared = False
+    tiles_used = 0
+
     def __init__(self, engine, buckets: Optional[List[int]] = None):
         self.engine = engine
         cfg = engine.cfg
@@ -63,6 +68,23 @@ class DecodeGraphRunner:
         self._row_nb = np.zeros(B, dtype=np.int32)
         self._row_gen = np.zeros(B, dtype=np.int64)
         self._arange = np.arange(B, dtype=np.int64)
+        # shared-prefix decode: static tile map + per-row prefix page counts
+        # + the f32 partial-state scratch, filled and copied with the rest
+        self.prefix_shared = bool(getattr(engine, "prefix_shared", False))
+        self.tiles_used = 0
+        if self.prefix_shared:
+            from .. import ops
+
+            hq, hk = engine.local_heads()
+            R = ops.prefix_tile_rows(hq, hk)
+            NT = max_tiles(B, R)
+            self.d_tile_rows = torch.full((NT, R), -1, dtype=torch.int32, device=dev)
+            self.d_rpp = torch.zeros(B, dtype=torch.int32, device=dev)
+            self.h_tile_rows = torch.full((NT, R), -1, dtype=torch.int32,
+                                          pin_memory=True)
+            self.h_rpp = torch.zeros(B, dtype=torch.int32, pin_memory=True)
+            self.d_partials = ops.alloc_prefix_partials(
+                B, hq, engine.spec.head_dim, dev)
         # async decode overwrites the pinned staging before any stream sync;
         # this event marks the previous step's H2D completion so the refill
         # never races an in-flight copy (waits ~0 in practice — the copies
@@ -88,7 +110,16 @@ class DecodeGraphRunner:
             tile_seq=self.d_tiles,
             tile_q0=self.d_tiles,
             prefill_token_count=0,
+            **self._prefix_fb(n),
         )
+
+    def _prefix_fb(self, n: int) -> dict:
+        if not self.prefix_shared:
+            return {}
+        nt = max_tiles(n, self.d_tile_rows.shape[1])
+        return dict(row_prefix_pages=self.d_rpp[:n],
+                    prefix_tile_rows=self.d_tile_rows[:nt],
+                    prefix_partials=tuple(t[:n] for t in self.d_partials))
 
     @torch.no_grad()
     def _capture_all(self) -> None:
@@ -132,6 +163,12 @@ class DecodeGraphRunner:
         self.d_slots[:bucket].copy_(self.h_slots[:bucket], non_blocking=True)
         self.d_bt[:bucket].copy_(self.h_bt[:bucket], non_blocking=True)
         self.d_sl[:bucket].copy_(self.h_sl[:bucket], non_blocking=True)
+        if self.prefix_shared:
+            nt = max_tiles(bucket, self.d_tile_rows.shape[1])
+            self.d_tile_rows[:nt].copy_(self.h_tile_rows[:nt], non_blocking=True)
+            self.d_rpp[:bucket].copy_(self.h_rpp[:bucket], non_blocking=True)
+            if self.tiles_used:
+                self.engine.prefix_tile_steps += 1
         if ids_override is not None:
             self.d_ids[:n].copy_(ids_override, non_blocking=True)
         if self._h2d_done is not None:
@@ -191,3 +228,12 @@ class DecodeGraphRunner:
             bt[n:bucket, 0] = scratch
             slots[n:bucket] = scratch * bs
             row_req[n:bucket] = -1
+
+        if self.prefix_shared:
+            # tiles of rows with common leading pages; padding rows and rows
+            # in no tile get P = 0 (the whole buffers are rewritten)
+            pb = kv.prefix_blocks
+            nb = np.fromiter((pb.get(r.req_id, 0) for r in sb.reqs), np.int64, n)
+            self.tiles_used = fill_prefix_tiles(
+                self.h_tile_rows.numpy(), self.h_rpp.numpy(), bt, sl, n, nb,
+                kv.allocator.ref, bs)

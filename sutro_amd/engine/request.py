@@ -136,6 +136,8 @@ class Request:
     # final text override: set when a stop STRING lands mid-token (BPE tokens
     # are multi-byte, so the trim point need not be a token boundary)
     text_override: Optional[str] = None
+    # prompt tokens served from the prefix cache at the latest admission
+    prefix_hit_tokens: int = 0
     _stop_ids: Optional[frozenset] = field(default=None, repr=False)
 
     def stop_ids(self, eos_id: int) -> frozenset:
@@ -168,6 +170,7 @@ class Request:
         caught by tests/test_scheduler_invariants.py). Seeded rows regenerate
         bit-identically."""
         self.num_computed_tokens = 0
+        self.prefix_hit_tokens = 0
         self.output_token_ids = []
         self.cumulative_logprob = 0.0
         self.text_override = None

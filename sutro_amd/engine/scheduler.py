@@ -36,6 +36,10 @@ class Scheduler:
         # abort, preemption): per-request device state tied to residency
         # (the penalty history slot) is given back here
         self.on_release: Optional[Callable[[Request], None]] = None
+        # prefix cache, cumulative: prompt tokens of admitted rows / of those,
+        # tokens found in the cache (re-admissions after preemption included)
+        self.prefix_query_tokens = 0
+        self.prefix_hit_tokens = 0
 
     # ---- queue management ----
 
@@ -176,7 +180,14 @@ class Scheduler:
         for q in (self.waiting_p0, self.waiting_p1):
             while q and budget > 0 and len(self.running) < self.cfg.max_num_seqs:
                 req = q[0]
-                need = req.num_prompt_tokens - req.num_computed_tokens
+                # prefix cache: the longest chain of registered blocks equal
+                # to the prompt's head is already computed — the row starts
+                # as a chunked prefill behind it
+                matched: List[int] = []
+                if self.kv.prefix_caching and req.num_computed_tokens == 0:
+                    matched = self.kv.match_prefix(req.prompt_token_ids)
+                start = max(req.num_computed_tokens, len(matched) * bs)
+                need = req.num_prompt_tokens - start
                 if (need > budget and decode_reqs
                         and need <= self.cfg.max_tokens_per_step):
                     # (prompts larger than a whole step budget must chunk
@@ -187,11 +198,23 @@ class Scheduler:
                     # hold the row for the next accumulated wave instead
                     break
                 c = min(need, budget)
-                blocks_needed = self.kv.blocks_needed(req.num_computed_tokens + c)
-                if blocks_needed > self.kv.allocator.num_free:
+                blocks_needed = self.kv.blocks_needed(start + c)
+                free_now = self.kv.allocator.num_free
+                if matched:
+                    # matched blocks nobody holds count as free until seeded
+                    blocks_needed -= len(matched)
+                    free_now -= self.kv.allocator.num_evictable_in(matched)
+                if blocks_needed > free_now:
                     break  # don't preempt running work to admit new work
                 q.popleft()
-                self.kv.grow(req.req_id, req.num_computed_tokens + c)
+                if self.kv.prefix_caching:
+                    self.prefix_query_tokens += req.num_prompt_tokens
+                if matched:
+                    self.kv.seed(req.req_id, matched)
+                    req.num_computed_tokens = start
+                    req.prefix_hit_tokens = start
+                    self.prefix_hit_tokens += start
+                self.kv.grow(req.req_id, start + c)
                 self.running.append(req)
                 prefill_reqs.append(req)
                 prefill_counts.append(c)

@@ -102,11 +102,20 @@ class Qwen3Attention(nn.Module):
             self.k_norm.weight if self.qk_norm else None,
             self.q_norm.eps if self.qk_norm else 1e-6,
         )
-        o = ops.paged_attention(q, kv.k_cache[self.layer_idx],
-                                kv.v_cache[self.layer_idx], fb.block_tables,
-                                fb.seq_lens, fb.query_start_locs, self.scale,
-                                fb.num_decodes_tail, fb.tile_seq, fb.tile_q0,
-                                fb.prefill_token_count)
+        if fb.prefix_tile_rows is not None:
+            # decode-only batch with shared-prefix tiles (the engine checked
+            # the tiles on the host when it built them)
+            o = ops.paged_attention_decode_shared(
+                q, kv.k_cache[self.layer_idx], kv.v_cache[self.layer_idx],
+                fb.block_tables, fb.seq_lens, self.scale,
+                fb.row_prefix_pages, fb.prefix_tile_rows, fb.prefix_partials,
+                validate=False)
+        else:
+            o = ops.paged_attention(q, kv.k_cache[self.layer_idx],
+                                    kv.v_cache[self.layer_idx], fb.block_tables,
+                                    fb.seq_lens, fb.query_start_locs, self.scale,
+                                    fb.num_decodes_tail, fb.tile_seq, fb.tile_q0,
+                                    fb.prefill_token_count)
         return self.tp.all_reduce(self.o_proj(o.view(T, self.q_size)))
 
 

@@ -210,6 +210,103 @@ def paged_attention(
                                      seq_lens, query_start_locs, scale)
 
 
+PREFIX_CB = 4  # column blocks per wave of attn_prefix_partial_kernel
+
+
+def prefix_tile_rows(num_heads: int, num_kv_heads: int) -> int:
+    """Rows per shared-prefix tile: the GQA group is padded to Gp in
+    {1,2,4,8} and a wave owns PREFIX_CB blocks of 16/Gp rows."""
+    g = num_heads // num_kv_heads
+    gp = 1
+    while gp < g:
+        gp *= 2
+    return PREFIX_CB * 16 // gp
+
+
+def shared_decode_supported(head_dim: int, num_heads: int, num_kv_heads: int,
+                            block_size: int = 32) -> bool:
+    """Where the MFMA decode route (and so the shared-prefix kernel) runs."""
+    return (head_dim in (64, 128) and block_size == 32
+            and num_heads % num_kv_heads == 0
+            and num_heads // num_kv_heads <= 8)
+
+
+def alloc_prefix_partials(n: int, num_heads: int, head_dim: int, device):
+    """f32 scratch the partial kernel hands to the per-row kernel:
+    (part_o [n, Hq, D] unnormalised, part_m [n, Hq], part_l [n, Hq])."""
+    return (torch.empty((n, num_heads, head_dim), dtype=torch.float32, device=device),
+            torch.empty((n, num_heads), dtype=torch.float32, device=device),
+            torch.empty((n, num_heads), dtype=torch.float32, device=device))
+
+
+def _check_shared_args(block_tables, seq_lens, row_prefix_pages, tile_rows,
+                       n: int, block_size: int) -> None:
+    """Host-side check of the caller's guarantees (eager mode only: it reads
+    the index tensors back)."""
+    bt = block_tables.cpu()
+    sl = seq_lens.cpu()
+    rp = row_prefix_pages.cpu()
+    tr = tile_rows.cpu()
+    assert int(rp[:n].min()) >= 0 and int(rp[:n].max()) <= bt.shape[1]
+    assert bool((sl[:n] > rp[:n] * block_size).all()), \
+        "every row needs a position beyond its shared prefix"
+    seen = set()
+    for t in range(tr.shape[0]):
+        rows = [int(r) for r in tr[t] if int(r) >= 0]
+        if not rows:
+            continue
+        assert all(r < n for r in rows), "tile row out of range"
+        p = int(rp[rows[0]])
+        assert p > 0, "tile rows need row_prefix_pages > 0"
+        for r in rows:
+            assert r not in seen, "row listed in two tiles"
+            seen.add(r)
+            assert int(rp[r]) == p and torch.equal(bt[r, :p], bt[rows[0], :p]), \
+                "rows of a tile must share their leading pages"
+    for r in range(n):
+        assert r in seen or int(rp[r]) == 0, \
+            "a row in no tile must have row_prefix_pages = 0"
+
+
+def paged_attention_decode_shared(
+    q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+    block_tables: torch.Tensor, seq_lens: torch.Tensor, scale: float,
+    row_prefix_pages: torch.Tensor, tile_rows: torch.Tensor,
+    partials=None, validate: Optional[bool] = None,
+) -> torch.Tensor:
+    """Decode-only paged attention (one query token per row) that walks the
+    KV pages a tile of rows has in common once per tile.
+
+    `row_prefix_pages` int32 [n]: leading pages of row i covered by its tile
+    (0 = none). `tile_rows` int32 [NT, prefix_tile_rows(Hq, Hk)]: row indices,
+    -1 = empty slot. The caller guarantees that the rows of a tile have the
+    same row_prefix_pages = P > 0 and identical first P table entries, that
+    rows in no tile have P = 0, and that every row has a position beyond its
+    prefix. The result is plain paged attention over the full tables —
+    bit-identical to `paged_attention` on the GPU."""
+    n = q.shape[0]
+    if _use_hip(q):
+        C = _require_hip()
+        if validate is None:
+            validate = not torch.cuda.is_current_stream_capturing()
+        if validate:
+            _check_shared_args(block_tables, seq_lens, row_prefix_pages,
+                               tile_rows, n, k_cache.shape[2])
+        if partials is None:
+            partials = alloc_prefix_partials(n, q.shape[1], q.shape[2], q.device)
+        out = torch.empty_like(q)
+        C.paged_attention_decode_shared(out, q, k_cache, v_cache, block_tables,
+                                        seq_lens, scale, row_prefix_pages,
+                                        tile_rows, *partials)
+        return out
+    if validate is None or validate:
+        _check_shared_args(block_tables, seq_lens, row_prefix_pages, tile_rows,
+                           n, k_cache.shape[2])
+    qlocs = torch.arange(n + 1, dtype=torch.int32, device=q.device)
+    return torch_ref.paged_attention(q, k_cache, v_cache, block_tables[:n],
+                                     seq_lens[:n], qlocs, scale)
+
+
 def mean_pool_normalize(hidden: torch.Tensor, query_start_locs: torch.Tensor) -> torch.Tensor:
     if _use_hip(hidden):
         S = query_start_locs.numel() - 1
