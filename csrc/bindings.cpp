@@ -74,6 +74,9 @@ void sutro_quant_weight_mxfp4(void*, void*, const void*, long, int, int,
 void sutro_grouped_gemm_mxfp4(void*, const void*, const float*, const void*,
                               const void*, const int*, const int*, const int*,
                               int, int, int, long, int, int, hipStream_t);
+int sutro_gemm_tn_fp8_pipe_launch(void*, const void*, const float*,
+                                  const void*, const float*, const void*, int,
+                                  int, long, int, int, hipStream_t);
 }
 
 void rmsnorm(torch::Tensor out, torch::Tensor x, torch::Tensor w, double eps) {
@@ -314,6 +317,75 @@ torch::Tensor gemm_gate_up_silu(torch::Tensor x, torch::Tensor w, long swz,
       out.data_ptr(), x.data_ptr(), w.data_ptr(), nullptr, (int)M, (int)N, K,
       2, (int)swz, (int)xcd_swz, cur_stream());
   TORCH_CHECK(e == 0, "gemm_gate_up_silu launch setup failed: ", e);
+  return out;
+}
+
+// shared operand checks of the two FP8 dense GEMM bindings
+static void check_fp8_gemm_args(const torch::Tensor& a_q,
+                                const torch::Tensor& a_scale,
+                                const torch::Tensor& w_q,
+                                const torch::Tensor& w_scale) {
+  CHECK_CUDA(a_q); CHECK_CONTIG(a_q); CHECK_CUDA(w_q); CHECK_CONTIG(w_q);
+  TORCH_CHECK(is_fp8(a_q) && is_fp8(w_q), "a_q, w_q must be float8_e4m3fn");
+  CHECK_CUDA(a_scale); CHECK_CONTIG(a_scale);
+  CHECK_CUDA(w_scale); CHECK_CONTIG(w_scale);
+  TORCH_CHECK(a_scale.scalar_type() == at::kFloat
+              && w_scale.scalar_type() == at::kFloat, "scales must be f32");
+  TORCH_CHECK(a_q.dim() == 2 && w_q.dim() == 2, "a_q and w_q must be 2-d");
+  const long M = a_q.size(0), Kp = a_q.size(1), N = w_q.size(0);
+  TORCH_CHECK(w_q.size(1) == Kp, "Kp mismatch");
+  TORCH_CHECK(M >= 1 && Kp >= 128 && Kp % 128 == 0,
+              "needs M >= 1 and Kp a positive multiple of 128 (Kp=", Kp, ")");
+  // the kernel rounds M and N up to the 256 tile in int
+  TORCH_CHECK(M <= (1L << 31) - 256 && N <= (1L << 31) - 256,
+              "M/N too large");
+  TORCH_CHECK(a_scale.numel() == M, "a_scale must be [M]");
+  TORCH_CHECK(w_scale.numel() == N, "w_scale must be [N]");
+}
+
+// out[M,N] bf16 = (a_q[M,Kp] @ w_q[N,Kp]^T) * a_scale[m] * w_scale[n]
+// (+ res, added in f32 before the one rounding) on the 8-phase pipelined
+// block-scaled MFMA kernel (csrc/gemm_tn_fp8_pipe.hip). Any M >= 1,
+// N % 64 == 0, Kp % 128 == 0.
+torch::Tensor gemm_fp8_pipelined(torch::Tensor a_q, torch::Tensor a_scale,
+                                 torch::Tensor w_q, torch::Tensor w_scale,
+                                 c10::optional<torch::Tensor> res,
+                                 long xcd_swz) {
+  check_fp8_gemm_args(a_q, a_scale, w_q, w_scale);
+  const long M = a_q.size(0), Kp = a_q.size(1), N = w_q.size(0);
+  TORCH_CHECK(N >= 64 && N % 64 == 0, "N must be a multiple of 64 (N=", N, ")");
+  auto out = torch::empty({M, N}, a_q.options().dtype(at::kBFloat16));
+  const void* rp = nullptr;
+  if (res.has_value()) {
+    CHECK_CUDA(*res); CHECK_BF16(*res);
+    TORCH_CHECK(res->is_contiguous() && res->dim() == 2 &&
+                res->size(0) == M && res->size(1) == N, "res shape");
+    rp = res->data_ptr();
+  }
+  const int e = sutro_gemm_tn_fp8_pipe_launch(
+      out.data_ptr(), a_q.data_ptr(), a_scale.data_ptr<float>(),
+      w_q.data_ptr(), w_scale.data_ptr<float>(), rp, (int)M, (int)N, Kp,
+      rp ? 1 : 0, (int)xcd_swz, cur_stream());
+  TORCH_CHECK(e == 0, "gemm_fp8_pipelined launch setup failed: ", e);
+  return out;
+}
+
+// out[M,I] = silu(g) * u, g / u the scaled products with the gate / up rows
+// of the merged w_q [2I, Kp]; f32 SwiGLU with one rounding (the grouped FP8
+// kernel's epilogue). I % 128 == 0.
+torch::Tensor gemm_fp8_gate_up_silu(torch::Tensor a_q, torch::Tensor a_scale,
+                                    torch::Tensor w_q, torch::Tensor w_scale,
+                                    long xcd_swz) {
+  check_fp8_gemm_args(a_q, a_scale, w_q, w_scale);
+  const long M = a_q.size(0), Kp = a_q.size(1), N = w_q.size(0);
+  TORCH_CHECK(N >= 256 && N % 256 == 0,
+              "gate_up rows must be 2*I with I % 128 == 0");
+  auto out = torch::empty({M, N / 2}, a_q.options().dtype(at::kBFloat16));
+  const int e = sutro_gemm_tn_fp8_pipe_launch(
+      out.data_ptr(), a_q.data_ptr(), a_scale.data_ptr<float>(),
+      w_q.data_ptr(), w_scale.data_ptr<float>(), nullptr, (int)M, (int)N, Kp,
+      2, (int)xcd_swz, cur_stream());
+  TORCH_CHECK(e == 0, "gemm_fp8_gate_up_silu launch setup failed: ", e);
   return out;
 }
 
@@ -690,4 +762,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "SwiGLU fused into the pipelined gate_up GEMM",
         py::arg("x"), py::arg("w"), py::arg("swz") = 2,
         py::arg("xcd_swz") = 1);
+  m.def("gemm_fp8_pipelined", &gemm_fp8_pipelined,
+        "e4m3 W8A8 TN GEMM (block-scaled MFMA, 8-phase glds pipeline)",
+        py::arg("a_q"), py::arg("a_scale"), py::arg("w_q"),
+        py::arg("w_scale"), py::arg("res") = c10::nullopt,
+        py::arg("xcd_swz") = 1);
+  m.def("gemm_fp8_gate_up_silu", &gemm_fp8_gate_up_silu,
+        "SwiGLU fused into the pipelined e4m3 gate_up GEMM",
+        py::arg("a_q"), py::arg("a_scale"), py::arg("w_q"),
+        py::arg("w_scale"), py::arg("xcd_swz") = 1);
 }

@@ -191,13 +191,21 @@ def models():
               type=click.Choice(["bf16", "fp8_e4m3", "mxfp4"]),
               help="storage of MoE expert weights (fp8_e4m3 halves them, "
                    "mxfp4 stores 4.25 bits per weight)")
-def serve(host: str, port: int, device: str, moe_weight_dtype: str):
+@click.option("--dense-weight-dtype", default="bf16",
+              type=click.Choice(["bf16", "fp8_e4m3"]),
+              help="storage of the dense projections (qkv, o, gate_up, down; "
+                   "fp8_e4m3 halves them and runs them W8A8)")
+def serve(host: str, port: int, device: str, moe_weight_dtype: str,
+          dense_weight_dtype: str):
     """Serve the HTTP API (the same endpoint contract as api.sutro.sh)."""
     from .service.http_api import run_server
 
-    engine_kwargs = None
+    engine_kwargs = {}
     if moe_weight_dtype != "bf16":
-        engine_kwargs = {"moe_weight_dtype": moe_weight_dtype}
+        engine_kwargs["moe_weight_dtype"] = moe_weight_dtype
+    if dense_weight_dtype != "bf16":
+        engine_kwargs["dense_weight_dtype"] = dense_weight_dtype
+    engine_kwargs = engine_kwargs or None
     run_server(host=host, port=port, device=device,
                engine_kwargs=engine_kwargs)
 

@@ -66,6 +66,14 @@ class EngineConfig:
     # "mxfp4": OCP MX e2m1 codes with one e8m0 scale per 32 K-elements (4.25
     # bits per weight), dequantised inside the block-scaled MFMA (W4A8).
     moe_weight_dtype: str = "bf16"
+    # "bf16" (default) or "fp8_e4m3": store the dense projections (qkv / o of
+    # every attention block, gate_up / down of every dense MLP) as OCP e4m3
+    # with f32 per-output-channel scales (quantised after load, per TP shard)
+    # and run them W8A8 on the pipelined block-scaled fp8 MFMA GEMM
+    # (csrc/gemm_tn_fp8_pipe.hip) — halves those bytes, which frees memory
+    # for KV. Embeddings / lm_head, norms, the MoE router and the experts
+    # keep their storage; independent of moe_weight_dtype.
+    dense_weight_dtype: str = "bf16"
     # block-hash prefix cache: full blocks of computed prompt tokens are
     # indexed by (parent block, token ids) and shared between rows by
     # reference count, so a job's common system prompt is prefilled and held
@@ -90,6 +98,10 @@ class EngineConfig:
             raise ValueError(
                 f"moe_weight_dtype must be 'bf16', 'fp8_e4m3' or 'mxfp4', "
                 f"got {self.moe_weight_dtype!r}")
+        if self.dense_weight_dtype not in ("bf16", "fp8_e4m3"):
+            raise ValueError(
+                f"dense_weight_dtype must be 'bf16' or 'fp8_e4m3', "
+                f"got {self.dense_weight_dtype!r}")
         if self.device == "cpu":
             self.dtype = torch.float32
         if self.max_model_len > self.spec.max_context:

@@ -109,6 +109,11 @@ class LLMEngine:
                 # hand the freed bf16 experts back to the driver so the KV
                 # sizing below sees them
                 torch.cuda.empty_cache()
+        if cfg.dense_weight_dtype == "fp8_e4m3":
+            self.model.quantize_dense_fp8()
+            if cfg.device.startswith("cuda"):
+                # likewise for the freed bf16 projections
+                torch.cuda.empty_cache()
 
         num_blocks = cfg.num_kv_blocks
         if num_blocks is None:

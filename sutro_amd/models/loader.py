@@ -186,6 +186,15 @@ def save_weights(model: torch.nn.Module, path: str) -> str:
     """Save the model's parameters as one safetensors file (testing/export)."""
     from safetensors.torch import save_file
 
+    for prefix, mod in model.named_modules():
+        if (isinstance(mod, torch.nn.Linear)
+                and mod.weight.dtype == torch.float8_e4m3fn):
+            # quantised dense projections are buffers, not parameters: the
+            # file would silently lack them, and no loader reads them back
+            raise RuntimeError(
+                f"{prefix}.weight is stored as fp8_e4m3 "
+                "(dense_weight_dtype): save the unquantised model; "
+                "checkpoints of FP8 dense weights are not supported")
     os.makedirs(path, exist_ok=True)
     out = os.path.join(path, "model.safetensors")
     state = {k: v.detach().cpu().contiguous()

@@ -47,6 +47,38 @@ def _mark_shard(p: nn.Parameter, full_shape, dim: int, tp: TPContext,
     p._tp_sections = row_sections
 
 
+@torch.no_grad()
+def _quantize_linear_fp8(lin: nn.Linear) -> None:
+    """Replace lin.weight [N, K] by OCP e4m3 codes [N, Kp] (K zero-padded to
+    the 128-element K-tile, a buffer under the same name) plus f32
+    per-output-channel scales `weight_scale` [N]; the unquantised tensor is
+    released. Idempotent; refuses a weight that is neither."""
+    w = lin.weight
+    if w.dtype == torch.float8_e4m3fn:
+        return
+    if w.dtype not in (torch.bfloat16, torch.float16, torch.float32):
+        raise RuntimeError(
+            f"weight is stored as {w.dtype}; fp8_e4m3 needs the unquantised "
+            "weights")
+    w = w.data.contiguous()
+    N, K = w.shape
+    w_q = torch.empty(N, torch_ref.fp8_padded_k(K), dtype=torch.float8_e4m3fn,
+                      device=w.device)
+    scale = torch.empty(N, dtype=torch.float32, device=w.device)
+    ops.quantize_rows_fp8(w, w_q, scale)
+    del lin._parameters["weight"]
+    del w
+    lin.register_buffer("weight", w_q)
+    lin.register_buffer("weight_scale", scale)
+
+
+def _dense_linear(lin: nn.Linear, x: torch.Tensor) -> torch.Tensor:
+    """lin(x), through the W8A8 kernel when lin was quantised."""
+    if lin.weight.dtype == torch.float8_e4m3fn:
+        return ops.linear_fp8(x, lin.weight, lin.weight_scale)
+    return lin(x)
+
+
 class RMSNorm(nn.Module):
     def __init__(self, size: int, eps: float, dtype: torch.dtype):
         super().__init__()
@@ -90,10 +122,22 @@ class Qwen3Attention(nn.Module):
             self.q_norm = RMSNorm(self.head_dim, spec.rms_eps, dtype)
             self.k_norm = RMSNorm(self.head_dim, spec.rms_eps, dtype)
 
+    @torch.no_grad()
+    def quantize_dense_fp8(self) -> None:
+        """Store qkv_proj / o_proj as e4m3 codes + f32 per-output-channel
+        scales (`weight`, `weight_scale`) and run them on ops.linear_fp8.
+        Acts on the LOCAL shard after TP sharding: the row-parallel o_proj
+        carries its own channel scales into the existing all-reduce. A
+        projection whose width the kernel does not take (N % 64) stays as it
+        is. Idempotent."""
+        for lin in (self.qkv_proj, self.o_proj):
+            if ops.linear_fp8_qualifies(*lin.weight.shape):
+                _quantize_linear_fp8(lin)
+
     def forward(self, x: torch.Tensor, fb: ForwardBatch, kv: PagedKVCache,
                 cos_sin: torch.Tensor) -> torch.Tensor:
         T = x.shape[0]
-        qkv = self.qkv_proj(x)
+        qkv = _dense_linear(self.qkv_proj, x)
         q = ops.fused_qkv_prep(
             qkv, self.num_heads, self.num_kv_heads, self.head_dim,
             fb.positions, fb.slot_mapping,
@@ -116,7 +160,8 @@ class Qwen3Attention(nn.Module):
                                     fb.seq_lens, fb.query_start_locs, self.scale,
                                     fb.num_decodes_tail, fb.tile_seq, fb.tile_q0,
                                     fb.prefill_token_count)
-        return self.tp.all_reduce(self.o_proj(o.view(T, self.q_size)))
+        return self.tp.all_reduce(
+            _dense_linear(self.o_proj, o.view(T, self.q_size)))
 
 
 class Qwen3MLP(nn.Module):
@@ -133,9 +178,28 @@ class Qwen3MLP(nn.Module):
         self.down_proj = nn.Linear(inter_l, hidden, bias=False, dtype=dtype)
         _mark_shard(self.down_proj.weight, (hidden, intermediate), 1, tp)
 
+    @torch.no_grad()
+    def quantize_dense_fp8(self) -> None:
+        """Store gate_up_proj / down_proj as e4m3 codes + f32 per-output-
+        channel scales (`weight`, `weight_scale`): gate_up then runs on
+        ops.gate_up_silu_fp8 (f32 SwiGLU, one rounding; GATE_UP_FUSED_RULE is
+        not consulted), down on ops.linear_fp8. Acts on the LOCAL shard after
+        TP sharding, like Qwen3MoE.quantize_experts_fp8; the bf16 tensor of
+        each projection is freed before the next one is quantised. A
+        projection the kernel does not take (gate_up: I % 128, down: N % 64)
+        stays as it is. Idempotent."""
+        if ops.gate_up_silu_fp8_qualifies(*self.gate_up_proj.weight.shape):
+            _quantize_linear_fp8(self.gate_up_proj)
+        if ops.linear_fp8_qualifies(*self.down_proj.weight.shape):
+            _quantize_linear_fp8(self.down_proj)
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        act = ops.gate_up_silu(x, self.gate_up_proj.weight)
-        return self.tp.all_reduce(self.down_proj(act))
+        gu = self.gate_up_proj
+        if gu.weight.dtype == torch.float8_e4m3fn:
+            act = ops.gate_up_silu_fp8(x, gu.weight, gu.weight_scale)
+        else:
+            act = ops.gate_up_silu(x, gu.weight)
+        return self.tp.all_reduce(_dense_linear(self.down_proj, act))
 
 
 class Qwen3MoE(nn.Module):
@@ -714,6 +778,16 @@ class Qwen3Model(nn.Module):
             x, residual = layer(x, residual, fb, kv, self.cos_sin)
         x, _ = ops.fused_add_rmsnorm(x, residual, self.norm.weight, self.norm.eps)
         return x  # [T, hidden]
+
+    @torch.no_grad()
+    def quantize_dense_fp8(self) -> None:
+        """W8A8 dense projections: qkv / o of every attention block and
+        gate_up / down of every dense MLP. Embeddings, lm_head, norms, the
+        MoE router and the experts (which have their own switch) keep their
+        storage."""
+        for mod in self.modules():
+            if isinstance(mod, (Qwen3Attention, Qwen3MLP)):
+                mod.quantize_dense_fp8()
 
     @torch.no_grad()
     def compute_logits(self, hidden: torch.Tensor) -> torch.Tensor:

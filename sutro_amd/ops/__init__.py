@@ -367,6 +367,45 @@ def grouped_gemm_fp8(out, a_q, a_scale, w_q, w_scale, row_tok, tile_off,
                                       gate_silu, bm)
 
 
+def linear_fp8_qualifies(n: int, k: int) -> bool:
+    """Weight shapes [n, k] the FP8 dense kernel takes (plain / residual
+    epilogue): N % 64 == 0; K % 8 == 0 is the row quantiser's 16-byte load."""
+    return n >= 64 and n % 64 == 0 and k >= 8 and k % 8 == 0
+
+
+def gate_up_silu_fp8_qualifies(two_i: int, k: int) -> bool:
+    """Merged gate_up shapes [2I, k] the FP8 SwiGLU epilogue takes:
+    I % 128 == 0."""
+    return two_i >= 256 and two_i % 256 == 0 and k >= 8 and k % 8 == 0
+
+
+def linear_fp8(x, w_q, w_scale, residual=None):
+    """Dense W8A8 projection: x [T, K] (bf16 on GPU) through w_q [N, Kp] e4m3
+    with f32 per-output-channel scales w_scale [N]; returns [T, N] in x's
+    dtype, optionally + residual (added in f32 before the one rounding).
+    Arithmetic: torch_ref.linear_fp8. On GPU the row quantiser runs as its
+    own pass, then csrc/gemm_tn_fp8_pipe.hip; no host sync, every tensor from
+    the caching allocator."""
+    if _use_hip(x):
+        C = _require_hip()
+        # fresh caching-allocator tensors: safe under hipGraph capture
+        x_q, x_s = torch_ref.quantize_act_fp8(x, quantize_rows_fp8)
+        return C.gemm_fp8_pipelined(x_q, x_s, w_q, w_scale, residual)
+    return torch_ref.linear_fp8(x, w_q, w_scale, residual)
+
+
+def gate_up_silu_fp8(x, w_q, w_scale):
+    """SwiGLU of the merged W8A8 gate_up projection (w_q [2I, Kp], gate rows
+    first): one kernel, f32 SwiGLU on the scaled products, one rounding.
+    Arithmetic: torch_ref.gate_up_silu_fp8."""
+    if _use_hip(x):
+        C = _require_hip()
+        # fresh caching-allocator tensors: safe under hipGraph capture
+        x_q, x_s = torch_ref.quantize_act_fp8(x, quantize_rows_fp8)
+        return C.gemm_fp8_gate_up_silu(x_q, x_s, w_q, w_scale)
+    return torch_ref.gate_up_silu_fp8(x, w_q, w_scale)
+
+
 def quantize_weight_mxfp4(w):
     """w [..., K] -> MXFP4 (e2m1 code pairs uint8 [..., Kp/2], e8m0 block
     scales uint8 [..., Kp/32]); the format and rule are stated in

@@ -221,6 +221,49 @@ def fp8_linear(a_q, a_scale, w_q, w_scale):
     return acc * a_scale.unsqueeze(1) * w_scale.unsqueeze(0)
 
 
+def quantize_act_fp8(x, quantize_rows=None):
+    """x [T, K] -> (e4m3 codes [T, Kp], f32 row scales [T]) in fresh tensors,
+    through `quantize_rows` (default: `quantize_rows_fp8` above; the op layer
+    passes its dispatching one, so the GPU path shares this helper)."""
+    T, K = x.shape
+    x_q = torch.empty(T, fp8_padded_k(K), dtype=torch.float8_e4m3fn,
+                      device=x.device)
+    x_s = torch.empty(T, dtype=torch.float32, device=x.device)
+    return (quantize_rows or quantize_rows_fp8)(x.contiguous(), x_q, x_s)
+
+
+def linear_fp8(x, w_q, w_scale, residual=None):
+    """THE statement of the dense W8A8 projection (csrc/gemm_tn_fp8_pipe.hip):
+    x [T, K] -> out [T, N] in x's dtype, for w_q [N, Kp] e4m3 + w_scale [N]
+    f32 (one scale per output channel, `quantize_weight_fp8` of the local
+    shard):
+
+        x_q, x_s = quantize_rows_fp8(x)              (per-row, amax / 448)
+        y        = fp8_linear(x_q, x_s, w_q, w_scale)   (f32)
+        y        = y + f32(residual)                  (when given)
+        out      = y rounded once to x's dtype"""
+    x_q, x_s = quantize_act_fp8(x)
+    y = fp8_linear(x_q, x_s, w_q, w_scale)
+    if residual is not None:
+        y = y + residual.float()
+    return y.to(x.dtype)
+
+
+def gate_up_silu_fp8(x, w_q, w_scale):
+    """SwiGLU of the merged W8A8 gate_up projection: w_q [2I, Kp] (gate rows
+    first) + w_scale [2I]; returns [T, I] in x's dtype.
+
+        y   = fp8_linear(quantize_rows_fp8(x), w_q, w_scale)    (f32 [T, 2I])
+        out = silu(y[:, :I]) * y[:, I:] in f32, rounded once
+
+    Unlike the bf16 gate_up path, the two products are NOT rounded before the
+    activation (the grouped FP8 kernel's epilogue)."""
+    x_q, x_s = quantize_act_fp8(x)
+    y = fp8_linear(x_q, x_s, w_q, w_scale)
+    inter = w_q.shape[0] // 2
+    return (torch.nn.functional.silu(y[:, :inter]) * y[:, inter:]).to(x.dtype)
+
+
 def grouped_gemm_fp8(out, a_q, a_scale, w_q, w_scale, row_tok, tile_off,
                      counts, max_tiles, gate_silu, bm: int = 64):
     """Reference for grouped_gemm_fp8 (csrc/grouped_gemm_fp8.hip) and the CPU
