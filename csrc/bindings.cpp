@@ -45,7 +45,9 @@ void sutro_mfma32_probe(float*, const void*, const void*, hipStream_t);
 void sutro_gemm_tn_launch(void*, const void*, const void*, const void*, int,
                           int, long, int, int, int, int, hipStream_t);
 int sutro_gemm_tn_pipe_launch(void*, const void*, const void*, const void*,
-                              int, int, long, int, int, int, hipStream_t);
+                              int, int, long, int, int, int, hipStream_t,
+                              int variant = 0, int group_m = 0,
+                              int num_blocks = 0, int wide = 0);
 void sutro_mfma16_probe(float*, const void*, const void*, hipStream_t);
 void sutro_hd64_stage_probe(float*, float*, void*, const void*, const void*,
                             const void*, int, float, hipStream_t);
@@ -300,8 +302,16 @@ torch::Tensor gemm_tn_pipelined(torch::Tensor x, torch::Tensor w,
 // w [2I, K] (gate rows first), fused into the pipelined GEMM's epilogue.
 // Both products are rounded to bf16 before the activation, so the result
 // equals gemm_tn_pipelined followed by silu_mul bit for bit.
+// variant 0: one tile per block; 1: the persistent kernel (K % 128 == 0) on
+// num_blocks blocks (0 = one per CU, -1 = one per tile), wide = dwordx4
+// epilogue stores.
+// group_m > 0 numbers the tiles in groups of that many M-tiles, group_m < 0
+// gives each XCD a band of M-tiles walked in groups of -group_m (both
+// variants). Every combination returns the same bits; the defaults are the
+// one-tile kernel in its plain order.
 torch::Tensor gemm_gate_up_silu(torch::Tensor x, torch::Tensor w, long swz,
-                                long xcd_swz) {
+                                long xcd_swz, long variant, long group_m,
+                                long num_blocks, bool wide) {
   CHECK_CUDA(x); CHECK_BF16(x); CHECK_CUDA(w); CHECK_BF16(w);
   TORCH_CHECK(x.dim() == 2 && w.dim() == 2, "x and w must be 2-d");
   TORCH_CHECK(x.is_contiguous() && w.is_contiguous(), "contiguous required");
@@ -312,10 +322,28 @@ torch::Tensor gemm_gate_up_silu(torch::Tensor x, torch::Tensor w, long swz,
               "gate_up rows must be 2*I with I % 128 == 0");
   TORCH_CHECK(M < (1L << 31) && N < (1L << 31), "M/N too large");
   TORCH_CHECK(swz >= 0 && swz <= 2, "swz must be 0, 1 or 2");
+  TORCH_CHECK(variant == 0 || variant == 1,
+              "variant must be 0 (one tile per block) or 1 (persistent)");
+  TORCH_CHECK(group_m > -(1L << 24) && group_m < (1L << 24),
+              "group_m out of range");
+  TORCH_CHECK(group_m >= 0 || xcd_swz != 0,
+              "the banded tile order (group_m < 0) needs xcd_swz");
+  TORCH_CHECK(num_blocks >= -1 && num_blocks <= (1L << 20),
+              "num_blocks out of range");
+  TORCH_CHECK(((M + 255) / 256) * (N / 256) < (1L << 31), "too many tiles");
+  if (variant == 1) {
+    TORCH_CHECK(K % 128 == 0 && K <= (1L << 23),
+                "the persistent gate_up kernel needs K % 128 == 0 (got K = ",
+                K, "); use variant 0");
+  } else {
+    TORCH_CHECK(num_blocks == 0 && !wide,
+                "num_blocks / wide apply to the persistent variant only");
+  }
   auto out = torch::empty({M, N / 2}, x.options());
   const int e = sutro_gemm_tn_pipe_launch(
       out.data_ptr(), x.data_ptr(), w.data_ptr(), nullptr, (int)M, (int)N, K,
-      2, (int)swz, (int)xcd_swz, cur_stream());
+      2, (int)swz, (int)xcd_swz, cur_stream(), (int)variant, (int)group_m,
+      (int)num_blocks, wide ? 1 : 0);
   TORCH_CHECK(e == 0, "gemm_gate_up_silu launch setup failed: ", e);
   return out;
 }
@@ -761,7 +789,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_gate_up_silu", &gemm_gate_up_silu,
         "SwiGLU fused into the pipelined gate_up GEMM",
         py::arg("x"), py::arg("w"), py::arg("swz") = 2,
-        py::arg("xcd_swz") = 1);
+        py::arg("xcd_swz") = 1, py::arg("variant") = 0,
+        py::arg("group_m") = 0, py::arg("num_blocks") = 0,
+        py::arg("wide") = false);
   m.def("gemm_fp8_pipelined", &gemm_fp8_pipelined,
         "e4m3 W8A8 TN GEMM (block-scaled MFMA, 8-phase glds pipeline)",
         py::arg("a_q"), py::arg("a_scale"), py::arg("w_q"),

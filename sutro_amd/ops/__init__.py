@@ -98,6 +98,71 @@ def set_gate_up_fused(mode: Optional[bool]) -> None:
     _GATE_UP_FORCE = mode
 
 
+# Which fused kernel a routed (K, 2I, M) runs: (K, 2I) -> list of
+# (min_M, max_M, variant, group_m, wide), first match wins, max_M None = no
+# upper end; no match = "v1", the one-tile-per-block kernel in its plain tile
+# order. variant 1 is the persistent kernel (seam prefetch), wide its dwordx4
+# epilogue stores; group_m is the tile order of either kernel: > 0 groups of
+# that many M-tiles, < 0 one band of M-tiles per XCD walked in groups of
+# -group_m (csrc/gemm_tn_pipe.hip). Every
+# variant returns the same bits, so this table is a speed choice only; it is
+# consulted only for shapes GATE_UP_FUSED_RULE routes to the fused kernel and
+# is filled from profiles/PROFILES.md capture G2 by G1's margin (median
+# better than v1's by more than twice the larger min-max spread at every
+# measured M of the range).
+GATE_UP_VARIANT_RULE: dict = {
+    # Qwen3-32B prefill waves: the one-tile kernel in the XCD-banded order,
+    # groups of 8 M-tiles (the persistent kernel and the wide stores cleared
+    # the margin against it nowhere, G2)
+    (5120, 51200): [(8192, 32768, 0, -8, False)],
+}
+_V1 = (0, 0, False)
+
+
+def _parse_variant(text: str):
+    """"v1" | "persistent[,group_m[,wide]]" -> (variant, group_m, wide)."""
+    parts = [p.strip() for p in text.split(",")]
+    if parts[0] == "v1" and len(parts) == 1:
+        return _V1
+    if parts[0] == "persistent" and len(parts) <= 3:
+        group_m = int(parts[1]) if len(parts) > 1 and parts[1] else 0
+        wide = len(parts) > 2 and parts[2] == "wide"
+        if len(parts) > 2 and parts[2] not in ("", "wide"):
+            raise ValueError(f"bad gate_up variant {text!r}")
+        return (1, group_m, wide)
+    raise ValueError(f"bad gate_up variant {text!r}: expected 'v1' or "
+                     "'persistent[,group_m[,wide]]'")
+
+
+# SUTRO_GATE_UP_VARIANT=v1 forces the one-tile kernel wherever the fused
+# kernel runs, =persistent[,group_m[,wide]] the persistent one (A/B only);
+# unset follows GATE_UP_VARIANT_RULE.
+_GATE_UP_VARIANT_FORCE = (
+    _parse_variant(os.environ["SUTRO_GATE_UP_VARIANT"])
+    if os.environ.get("SUTRO_GATE_UP_VARIANT") else None)
+
+
+def set_gate_up_variant(mode) -> None:
+    """In-process form of SUTRO_GATE_UP_VARIANT: the same string, or None to
+    restore the measured table."""
+    global _GATE_UP_VARIANT_FORCE
+    _GATE_UP_VARIANT_FORCE = None if mode is None else _parse_variant(mode)
+
+
+def gate_up_variant(k: int, two_i: int, m: int):
+    """(variant, group_m, wide) of the fused kernel for a routed shape. The
+    persistent kernel needs K % 128 == 0; other K stay on v1."""
+    if k % 128 != 0:
+        return _V1
+    if _GATE_UP_VARIANT_FORCE is not None:
+        return _GATE_UP_VARIANT_FORCE
+    for lo, hi, variant, group_m, wide in GATE_UP_VARIANT_RULE.get(
+            (k, two_i), ()):
+        if m >= lo and (hi is None or m <= hi):
+            return (variant, group_m, wide)
+    return _V1
+
+
 def gate_up_silu_qualifies(x: torch.Tensor, weight: torch.Tensor) -> bool:
     """Shapes the fused kernel takes: bf16, contiguous, K % 64 == 0 and
     I % 128 == 0 (weight is the merged [2I, K], gate rows first)."""
@@ -124,7 +189,11 @@ def gate_up_silu(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
         else:
             fused = _GATE_UP_FORCE
         if fused:
-            return _require_hip().gemm_gate_up_silu(x, weight)
+            v = gate_up_variant(x.shape[1], weight.shape[0], x.shape[0])
+            if v == _V1:
+                return _require_hip().gemm_gate_up_silu(x, weight)
+            return _require_hip().gemm_gate_up_silu(
+                x, weight, 2, 1, v[0], v[1], 0, v[2])
     return silu_mul(torch.nn.functional.linear(x, weight))
 
 

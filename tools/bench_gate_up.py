@@ -8,7 +8,14 @@ call so no call finds its weights in the last-level cache; the TunableOp
 table is loaded the way the engine loads it.
 
     python tools/bench_gate_up.py [--rounds 5] [--calls 20] [--quick]
-Writes bench_outputs/gate_up_bench.txt (or under $BENCH_OUT)."""
+    python tools/bench_gate_up.py --variant-sweep [M,M,..]
+Writes bench_outputs/gate_up_bench.txt (or under $BENCH_OUT).
+
+--variant-sweep compares the fused kernel's variants on the 32B shape (same
+method): the one-tile kernel ("v1"), v1 in the grouped tile order, the
+persistent kernel, persistent + grouped order, and that with wide epilogue
+stores, group_m in {4, 8, 16}, the wide stores on one block per tile, and
+the XCD-banded order (group_m = -8) on both kernels; writes gate_up_variant_sweep.txt."""
 
 import argparse
 import os
@@ -57,6 +64,30 @@ def variants(M):
     ]
 
 
+# the M of capture G2: the routed decode buckets, the prefill waves, and the
+# held-back buckets 1536 / 1664 / 1792 (for information only)
+SWEEP_M = [1152, 1280, 1408, 1920, 2048, 3072, 4096, 8192, 16384, 30976,
+           32768, 1536, 1664, 1792]
+GROUP_MS = (4, 8, 16)
+
+
+def sweep_variants():
+    def fused(variant, group_m, wide, num_blocks=0):
+        return lambda x, w: _C.gemm_gate_up_silu(x, w, 2, 1, variant, group_m,
+                                                 num_blocks, wide)
+    vs = [("v1", fused(0, 0, False))]
+    vs += [(f"v1 g{g}", fused(0, g, False)) for g in GROUP_MS]
+    vs += [("v1 banded g8", fused(0, -8, False))]
+    vs += [("persistent", fused(1, 0, False))]
+    vs += [(f"persistent g{g}", fused(1, g, False)) for g in GROUP_MS]
+    vs += [(f"persistent g{g} wide", fused(1, g, True)) for g in GROUP_MS]
+    # the persistent kernel's code on one block per tile: the wide stores
+    # without the static tile walk
+    vs += [("block per tile g8 wide", fused(1, 8, True, -1))]
+    vs += [("persistent banded g8 wide", fused(1, -8, True))]
+    return vs
+
+
 def window(fn, xs, ws, calls):
     start = torch.cuda.Event(enable_timing=True)
     end = torch.cuda.Event(enable_timing=True)
@@ -77,6 +108,10 @@ def main():
     ap.add_argument("--route-sweep", type=str, default=None, metavar="M,M,..",
                     help="library pair vs fused on the 32B shape at these M "
                          "(for the routing threshold)")
+    ap.add_argument("--variant-sweep", type=str, default=None, nargs="?",
+                    const=",".join(map(str, SWEEP_M)), metavar="M,M,..",
+                    help="the fused kernel's variants on the 32B shape at "
+                         "these M (default: the M of capture G2)")
     args = ap.parse_args()
 
     _setup_tunableop(EngineConfig(spec=get_model_spec("qwen-3-32b"),
@@ -90,9 +125,9 @@ def main():
     emit(f"rounds={args.rounds} calls/window={args.calls} weight sets={NSETS}"
          f" device={torch.cuda.get_device_name(0)}")
     shapes = [s for s in SHAPES if not args.quick or s[:2] == ("32b", 2048)]
-    if args.route_sweep:
+    if args.route_sweep or args.variant_sweep:
         shapes = [("32b", int(m), 25600, 5120)
-                  for m in args.route_sweep.split(",")]
+                  for m in (args.route_sweep or args.variant_sweep).split(",")]
     for label, M, I, K in shapes:
         g = torch.Generator(device="cuda")
         g.manual_seed(M + I)
@@ -103,6 +138,8 @@ def main():
         vs = variants(M)
         if args.route_sweep:
             vs = [vs[0], vs[4]]
+        if args.variant_sweep:
+            vs = sweep_variants()
         times = {name: [] for name, _ in vs}
         for r in range(args.rounds + 1):  # round 0 warms up
             for name, fn in vs:
@@ -122,7 +159,9 @@ def main():
 
     outd = os.environ.get("BENCH_OUT", "bench_outputs")
     os.makedirs(outd, exist_ok=True)
-    name = "gate_up_route_sweep.txt" if args.route_sweep else "gate_up_bench.txt"
+    name = ("gate_up_route_sweep.txt" if args.route_sweep else
+            "gate_up_variant_sweep.txt" if args.variant_sweep else
+            "gate_up_bench.txt")
     with open(os.path.join(outd, name), "w") as f:
         f.write("\n".join(lines) + "\n")
 
