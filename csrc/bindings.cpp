@@ -18,7 +18,7 @@ static hipStream_t cur_stream() {
 extern "C" {
 void sutro_rmsnorm(void*, const void*, const void*, float, long, int,
                    hipStream_t);
-void sutro_fused_add_rmsnorm(void*, void*, const void*, float, long, int,
+void sutro_fused_add_rmsnorm(void*, void*, const void*, float, long, int, int,
                              hipStream_t);
 void sutro_silu_mul(void*, const void*, long, int, hipStream_t);
 void sutro_rope_and_cache(void*, void*, const void*, const long*, const long*,
@@ -32,10 +32,11 @@ void sutro_mean_pool_normalize(float*, const void*, const int*, int, int,
 void sutro_attn_decode(void*, const void*, const void*, const void*,
                        const int*, const int*, int, int, int, int, int, int,
                        int, float, hipStream_t);
-void sutro_attn_prefill(void*, const void*, const void*, const void*,
-                        const int*, const int*, const int*, const int*,
-                        const int*, int, int, int, int, int, int, float,
-                        hipStream_t);
+int sutro_attn_prefill(void*, const void*, const void*, const void*,
+                       const int*, const int*, const int*, const int*,
+                       const int*, int, int, int, int, int, int, float, int,
+                       int, hipStream_t);
+int sutro_attn_prefill_pipe_supported(int, int, int, int);
 void sutro_attn_decode_shared(void*, const void*, const void*, const void*,
                               const int*, const int*, int, int, int, int,
                               float, int, int, const int*, const int*, int,
@@ -91,13 +92,15 @@ void rmsnorm(torch::Tensor out, torch::Tensor x, torch::Tensor w, double eps) {
 }
 
 void fused_add_rmsnorm(torch::Tensor x, torch::Tensor residual, torch::Tensor w,
-                       double eps) {
+                       double eps, int64_t variant) {
   CHECK_CUDA(x); CHECK_CONTIG(x); CHECK_BF16(x); CHECK_CONTIG(residual);
   const long C = x.size(-1);
   const long rows = x.numel() / C;
   TORCH_CHECK(C % 8 == 0 && C <= 16384, "unsupported row size ", C);
+  TORCH_CHECK(variant == 0 || variant == 1, "rmsnorm variant 0 or 1");
   sutro_fused_add_rmsnorm(x.data_ptr(), residual.data_ptr(), w.data_ptr(),
-                          (float)eps, rows, (int)C, cur_stream());
+                          (float)eps, rows, (int)C, (int)variant,
+                          cur_stream());
 }
 
 void silu_mul(torch::Tensor out, torch::Tensor x) {
@@ -139,7 +142,8 @@ void paged_attention(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
                      torch::Tensor v_cache, torch::Tensor block_tables,
                      torch::Tensor seq_lens, torch::Tensor qlocs, double scale,
                      int64_t num_decodes, torch::Tensor tile_seq,
-                     torch::Tensor tile_q0, int64_t prefill_token_count) {
+                     torch::Tensor tile_q0, int64_t prefill_token_count,
+                     int64_t tile_rows, int64_t prefill_variant) {
   CHECK_CUDA(q); CHECK_CONTIG(q); CHECK_BF16(q); CHECK_CONTIG(k_cache);
   const int Hq = q.size(1), D = q.size(2);
   const int Hk = k_cache.size(1);
@@ -153,12 +157,20 @@ void paged_attention(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
   const int bt_stride = block_tables.size(1);
   const int n_tiles = tile_seq.numel();
   if (n_tiles > 0) {
-    sutro_attn_prefill(out.data_ptr(), q.data_ptr(), k_cache.data_ptr(),
-                       v_cache.data_ptr(), block_tables.data_ptr<int>(),
-                       seq_lens.data_ptr<int>(), qlocs.data_ptr<int>(),
-                       tile_seq.data_ptr<int>(), tile_q0.data_ptr<int>(),
-                       n_tiles, bt_stride, Hq, Hk, D,
-                       is_fp8(k_cache) ? 1 : 0, (float)scale, cur_stream());
+    // prefill_variant 0: the one-tile-per-block kernel (32-row tiles);
+    // 1: the pipelined kernel, tile lists built at a step of tile_rows
+    const int rc = sutro_attn_prefill(
+        out.data_ptr(), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+        block_tables.data_ptr<int>(), seq_lens.data_ptr<int>(),
+        qlocs.data_ptr<int>(), tile_seq.data_ptr<int>(),
+        tile_q0.data_ptr<int>(), n_tiles, bt_stride, Hq, Hk, D,
+        is_fp8(k_cache) ? 1 : 0, (float)scale, (int)tile_rows,
+        (int)prefill_variant, cur_stream());
+    TORCH_CHECK(rc != -2, "pipelined prefill attention: the LDS size was "
+                "refused or the launch failed");
+    TORCH_CHECK(rc == 0, "prefill attention variant ", prefill_variant,
+                " does not take tile_rows ", tile_rows, " with Hq ", Hq,
+                ", Hk ", Hk, ", head_dim ", D);
   }
   if (num_decodes > 0) {
     const long dec_off = prefill_token_count;  // decode rows are the tail
@@ -749,12 +761,25 @@ void logit_penalties(torch::Tensor logits, torch::Tensor row_idx,
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsnorm", &rmsnorm, "RMSNorm (bf16, CDNA4)");
-  m.def("fused_add_rmsnorm", &fused_add_rmsnorm, "residual+=x; x=rmsnorm");
+  m.def("fused_add_rmsnorm", &fused_add_rmsnorm, "residual+=x; x=rmsnorm",
+        py::arg("x"), py::arg("residual"), py::arg("w"), py::arg("eps"),
+        py::arg("variant") = 0);
   m.def("silu_mul", &silu_mul, "fused SwiGLU");
   m.def("rope_and_cache", &rope_and_cache, "RoPE + paged KV write");
   m.def("qkv_prep", &qkv_prep, "fused qk-norm + RoPE + KV write + q gather");
   m.def("mean_pool_normalize", &mean_pool_normalize, "varlen mean pool + L2");
-  m.def("paged_attention", &paged_attention, "paged prefill+decode attention");
+  m.def("paged_attention", &paged_attention, "paged prefill+decode attention",
+        py::arg("out"), py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("block_tables"), py::arg("seq_lens"), py::arg("qlocs"),
+        py::arg("scale"), py::arg("num_decodes"), py::arg("tile_seq"),
+        py::arg("tile_q0"), py::arg("prefill_token_count"),
+        py::arg("tile_rows") = 32, py::arg("prefill_variant") = 0);
+  m.def("attn_prefill_pipe_supported",
+        [](int64_t hq, int64_t hk, int64_t d, int64_t rows) {
+          return sutro_attn_prefill_pipe_supported((int)hq, (int)hk, (int)d,
+                                                   (int)rows) != 0;
+        },
+        "whether the pipelined prefill kernel takes (Hq, Hk, D, tile_rows)");
   m.def("paged_attention_decode_shared", &paged_attention_decode_shared,
         "decode attention, shared-prefix tiles + per-row continuation");
   m.def("prefix_tile_rows", &prefix_tile_rows,

@@ -41,10 +41,12 @@ class ForwardBatch:
     logits_idx: torch.Tensor       # [n] long - flat rows needing logits
     max_seq_len: int               # host-side max of seq_lens
     max_query_len: int             # host-side max new tokens per seq
-    # prefill q-tile map for the GPU flash kernel (32 rows per tile)
+    # prefill q-tile map for the GPU flash kernel (prefill_tile_rows rows per
+    # tile: ops.prefill_tile_step of the head layout)
     tile_seq: Optional[torch.Tensor] = None   # [n_tiles] int32 seq index
     tile_q0: Optional[torch.Tensor] = None    # [n_tiles] int32 local row start
     prefill_token_count: int = 0              # flat rows belonging to prefills
+    prefill_tile_rows: int = 32
     # shared-prefix decode (decode-only batches; None = ordinary attention):
     # leading pages of each row covered by its tile, the tiles' row indices
     # (-1 = empty slot), and the f32 partial-state scratch (o, m, l)

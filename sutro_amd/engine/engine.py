@@ -333,12 +333,17 @@ class LLMEngine:
         for s in range(sb.num_prefills, S):
             logits_rows.append(int(qlocs[s + 1]) - 1)
 
-        # prefill q-tile map (32 rows per tile) for the GPU flash kernel
+        # prefill q-tile map for the GPU flash kernel, at the granularity the
+        # routed kernel takes for this head layout
+        from .. import ops
+        tile_step = ops.prefill_tile_step(
+            *self.local_heads(), self.spec.head_dim,
+            max(sb.num_new_tokens[:sb.num_prefills], default=0))
         tiles_s: List[int] = []
         tiles_q0: List[int] = []
         for s in range(sb.num_prefills):
             c = sb.num_new_tokens[s]
-            for j in range(0, c, 32):
+            for j in range(0, c, tile_step):
                 tiles_s.append(s)
                 tiles_q0.append(j)
         prefill_token_count = int(qlocs[sb.num_prefills])
@@ -363,6 +368,7 @@ class LLMEngine:
             tile_seq=torch.tensor(tiles_s, dtype=torch.int32, device=dev),
             tile_q0=torch.tensor(tiles_q0, dtype=torch.int32, device=dev),
             prefill_token_count=prefill_token_count,
+            prefill_tile_rows=tile_step,
         )
 
     def _prefix_tiles_eager(self, sb: ScheduledBatch, block_tables: np.ndarray,

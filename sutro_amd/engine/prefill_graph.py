@@ -10,8 +10,8 @@ Padding is scratch-directed and kernel-verified:
 - pad tokens: slot_mapping -> the engine's reserved scratch KV block; their
   q/k/v outputs are garbage that nothing reads (they belong to no sequence).
 - pad tiles: tile_seq points at a dummy sequence with qlocs[s]==qlocs[s+1]
-  and seq_len 0, so the flash kernel computes nq=0 / ntiles_kv=0 and exits
-  without loads or stores (csrc/attn_prefill.hip:73-78,244).
+  and seq_len 0, so the flash kernels compute nq=0 / no KV pages and exit
+  without loads or stores (csrc/attn_prefill.hip).
 - pad block-table rows are zero and never dereferenced (ntiles_kv=0).
 
 The hidden-states output buffer is returned whole; logits for rows that
@@ -34,6 +34,9 @@ from .batch import ForwardBatch, ScheduledBatch
 
 
 class PrefillGraphRunner:
+    # rows per prefill q tile; __init__ sets the routed kernel's
+    tile_step = 32
+
     def __init__(self, engine):
         self.engine = engine
         cfg = engine.cfg
@@ -42,6 +45,10 @@ class PrefillGraphRunner:
         self.s_max = cfg.max_num_seqs + 1
         self.bt_width = (cfg.max_model_len + cfg.kv_block_size - 1) // cfg.kv_block_size
         self.tile_max = self.s_max + self.t_pad // 32
+        # rows per prefill q tile of the routed attention kernel
+        from .. import ops
+        self.tile_step = ops.prefill_tile_step(*engine.local_heads(),
+                                               engine.spec.head_dim)
         # replay only when the wave is big enough that padding waste is small
         self.min_tokens = cfg.graph_prefill_min_tokens
         self._h2d_done = (torch.cuda.Event()
@@ -75,6 +82,7 @@ class PrefillGraphRunner:
             max_seq_len=cfg.max_model_len, max_query_len=self.t_pad,
             tile_seq=self.d_tile_seq, tile_q0=self.d_tile_q0,
             prefill_token_count=self.t_pad,
+            prefill_tile_rows=self.tile_step,
         )
 
     @torch.no_grad()
@@ -102,6 +110,14 @@ class PrefillGraphRunner:
         torch.cuda.synchronize()
 
     def can_run(self, sb: ScheduledBatch) -> bool:
+        # the capture holds the kernel and tile granularity routed when it
+        # was made; if the routing was switched since (ops.set_attn_prefill),
+        # the wave runs eager
+        from .. import ops
+        eng = self.engine
+        if ops.prefill_tile_step(*eng.local_heads(),
+                                 eng.spec.head_dim) != self.tile_step:
+            return False
         return (self.graph is not None
                 and sb.num_prefills == len(sb.reqs)
                 and self.min_tokens <= sb.total_tokens <= self.t_pad
@@ -125,6 +141,7 @@ class PrefillGraphRunner:
 
         cursor = 0
         tiles = 0
+        tile_step = self.tile_step
         for s, (req, c) in enumerate(zip(sb.reqs, sb.num_new_tokens)):
             start = req.num_computed_tokens
             table = kv.block_tables[req.req_id]
@@ -137,7 +154,7 @@ class PrefillGraphRunner:
             sl[s] = start + c
             bt[s, :len(table)] = table
             bt[s, len(table):] = 0
-            for j in range(0, c, 32):
+            for j in range(0, c, tile_step):
                 tseq[tiles] = s
                 tq0[tiles] = j
                 tiles += 1

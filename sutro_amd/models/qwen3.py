@@ -159,7 +159,8 @@ class Qwen3Attention(nn.Module):
                                     kv.v_cache[self.layer_idx], fb.block_tables,
                                     fb.seq_lens, fb.query_start_locs, self.scale,
                                     fb.num_decodes_tail, fb.tile_seq, fb.tile_q0,
-                                    fb.prefill_token_count)
+                                    fb.prefill_token_count,
+                                    tile_rows=fb.prefill_tile_rows)
         return self.tp.all_reduce(
             _dense_linear(self.o_proj, o.view(T, self.q_size)))
 

@@ -53,10 +53,31 @@ def rmsnorm(x: torch.Tensor, weight: torch.Tensor, eps: float) -> torch.Tensor:
     return torch_ref.rmsnorm(x, weight, eps)
 
 
-def fused_add_rmsnorm(x, residual, weight, eps: float):
+# Row widths C at which fused_add_rmsnorm runs rmsnorm_wide_reg_kernel (row
+# held in registers, csrc/rmsnorm.hip) instead of rmsnorm_wide_kernel. Same
+# bits from both; listed are the widths measured to clear the project's
+# margin at every measured row count (profiles/PROFILES.md capture A1).
+RMSNORM_REG_RULE: frozenset = frozenset({5120})   # Qwen3-32B
+
+# SUTRO_RMSNORM=v1 forces the reference kernel, =reg the register one (A/B
+# only); unset follows RMSNORM_REG_RULE.
+_RMSNORM_FORCE: Optional[bool] = {"reg": True, "v1": False}.get(
+    os.environ.get("SUTRO_RMSNORM", ""))
+
+
+def fused_add_rmsnorm(x, residual, weight, eps: float,
+                      variant: Optional[str] = None):
+    """`variant`: "v1" / "reg" pick the kernel explicitly (tests, A/B)."""
     if _use_hip(x):
+        if variant is not None:
+            reg = {"reg": True, "v1": False}[variant]
+        elif _RMSNORM_FORCE is not None:
+            reg = _RMSNORM_FORCE
+        else:
+            reg = x.shape[-1] in RMSNORM_REG_RULE
         # in-place: residual += x; x_out = rmsnorm(residual)
-        _require_hip().fused_add_rmsnorm(x, residual, weight, eps)
+        _require_hip().fused_add_rmsnorm(x, residual, weight, eps,
+                                         1 if reg else 0)
         return x, residual
     return torch_ref.fused_add_rmsnorm(x, residual, weight, eps)
 
@@ -251,6 +272,90 @@ def rope_and_cache(
 _EMPTY_I32: Optional[torch.Tensor] = None
 
 
+# Prefill attention routing: (G, head_dim) -> rows per q tile of the
+# pipelined kernel (csrc/attn_prefill.hip, attn_prefill_pipe_kernel); a head
+# layout that is not listed runs the one-tile-per-block reference kernel on
+# 32-row tiles. Both kernels return the same bits, so this table is a speed
+# choice only. It is filled from profiles/PROFILES.md capture A1 by the
+# project's margin: a granularity is listed only where its median beat the
+# reference kernel's by more than twice the larger min-max spread of the two
+# at every measured shape, and of those the fastest at the wave shape.
+PREFILL_TILE_ROWS: tuple = (32, 64, 128)
+ATTN_PREFILL_RULE: dict = {
+    (8, 128): 64,   # Qwen3-32B: 8 waves, each walking two 32-row sub-tiles
+}
+
+# SUTRO_ATTN_PREFILL=v1 forces the reference kernel, =pipe[,rows] the
+# pipelined one at `rows` rows per tile (default 32) wherever it takes the
+# head layout (A/B only); unset follows ATTN_PREFILL_RULE.
+
+
+def _parse_attn_prefill(text: str):
+    """"v1" | "pipe[,rows]" -> None (reference kernel) or rows per tile."""
+    parts = [p.strip() for p in text.split(",")]
+    if parts == ["v1"]:
+        return None
+    if parts[0] == "pipe" and len(parts) <= 2:
+        rows = int(parts[1]) if len(parts) > 1 else 32
+        if rows in PREFILL_TILE_ROWS:
+            return rows
+    raise ValueError(f"bad prefill attention variant {text!r}: expected "
+                     "'v1' or 'pipe[,32|64|128]'")
+
+
+_ATTN_PREFILL_FORCE = (
+    (_parse_attn_prefill(os.environ["SUTRO_ATTN_PREFILL"]),)
+    if os.environ.get("SUTRO_ATTN_PREFILL") else None)
+
+
+def set_attn_prefill(mode) -> None:
+    """In-process form of SUTRO_ATTN_PREFILL: the same string, or None to
+    restore the measured table."""
+    global _ATTN_PREFILL_FORCE
+    _ATTN_PREFILL_FORCE = None if mode is None else (_parse_attn_prefill(mode),)
+
+
+def attn_prefill_pipe_supported(num_heads: int, num_kv_heads: int,
+                                head_dim: int, tile_rows: int) -> bool:
+    """Mirror of the kernel's own check: G <= 8 heads per kv head (one wave
+    each) and G * tile_rows / 32 (head, sub-tile) pairs per block of 1, 2, 4,
+    8 or 16."""
+    if num_kv_heads <= 0 or num_heads % num_kv_heads:
+        return False
+    if head_dim not in (64, 128) or tile_rows not in PREFILL_TILE_ROWS:
+        return False
+    g = num_heads // num_kv_heads
+    return g <= 8 and g * (tile_rows // 32) in (1, 2, 4, 8, 16)
+
+
+def prefill_tile_rows(num_heads: int, num_kv_heads: int,
+                      head_dim: int) -> Optional[int]:
+    """Rows per prefill q tile of the pipelined kernel for this head layout,
+    or None where the reference kernel runs (its tiles have 32 rows). Callers
+    build tile_seq / tile_q0 with a step of `prefill_tile_step(...)`."""
+    if _ATTN_PREFILL_FORCE is not None:
+        rows = _ATTN_PREFILL_FORCE[0]
+    else:
+        rows = ATTN_PREFILL_RULE.get(
+            (num_heads // max(num_kv_heads, 1), head_dim))
+    if rows is not None and attn_prefill_pipe_supported(
+            num_heads, num_kv_heads, head_dim, rows):
+        return rows
+    return None
+
+
+def prefill_tile_step(num_heads: int, num_kv_heads: int, head_dim: int,
+                      max_new_tokens: Optional[int] = None) -> int:
+    """Step at which the engine builds its prefill tile lists. A batch whose
+    longest chunk has at most 32 new tokens (`max_new_tokens`) is built at 32
+    rows even where the layout's rule names more: the further sub-tiles of
+    every block would be empty (measured in capture A1, seeded step)."""
+    rows = prefill_tile_rows(num_heads, num_kv_heads, head_dim) or 32
+    if max_new_tokens is not None and max_new_tokens <= 32:
+        return 32
+    return rows
+
+
 def paged_attention(
     q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
     block_tables: torch.Tensor, seq_lens: torch.Tensor,
@@ -259,21 +364,35 @@ def paged_attention(
     tile_seq: Optional[torch.Tensor] = None,
     tile_q0: Optional[torch.Tensor] = None,
     prefill_token_count: int = 0,
+    tile_rows: int = 32,
+    prefill_variant: Optional[str] = None,
 ) -> torch.Tensor:
     """Attention of new tokens vs full cached KV (causal within the new chunk).
 
     `num_decodes_tail`: trailing sequences that are single-token decodes (the
     GPU path routes them to the decode kernel). `tile_seq`/`tile_q0`: int32
-    device arrays mapping prefill q-tiles of 32 rows to (seq, local row)."""
+    device arrays mapping prefill q-tiles of `tile_rows` rows (32, 64 or 128)
+    to (seq, local row). `prefill_variant`: "v1" (reference kernel, 32-row
+    tiles only) or "pipe"; None picks by the routing above: tiles of more
+    than 32 rows need the pipelined kernel, 32-row tiles run it where the
+    rule (or the env switch) routes this head layout to it."""
     if _use_hip(q):
         out = torch.empty_like(q)
         if tile_seq is None:
             tile_seq = torch.empty(0, dtype=torch.int32, device=q.device)
             tile_q0 = tile_seq
+        if prefill_variant is None:
+            pipe = (tile_rows != 32 or prefill_tile_rows(
+                q.shape[1], k_cache.shape[1], q.shape[2]) is not None)
+        elif prefill_variant in ("v1", "pipe"):
+            pipe = prefill_variant == "pipe"
+        else:
+            raise ValueError(f"bad prefill_variant {prefill_variant!r}")
         _require_hip().paged_attention(out, q, k_cache, v_cache, block_tables,
                                        seq_lens, query_start_locs, scale,
                                        num_decodes_tail, tile_seq, tile_q0,
-                                       prefill_token_count)
+                                       prefill_token_count, tile_rows,
+                                       1 if pipe else 0)
         return out
     return torch_ref.paged_attention(q, k_cache, v_cache, block_tables,
                                      seq_lens, query_start_locs, scale)
