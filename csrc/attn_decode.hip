@@ -366,6 +366,39 @@ extern "C" void sutro_attn_decode_mfma(void*, const void*, const void*,
                                        int, int, int, int, int, float, int,
                                        int, hipStream_t);
 
+extern "C" void sutro_attn_decode_mfma_local(void*, const void*, const void*,
+                                             const void*, const int*,
+                                             const int*, int, int, int, int,
+                                             int, float, int, int, int,
+                                             const float*, hipStream_t);
+
+// whether a decode call runs the MFMA kernel (the only one with a window and
+// sinks) or the VALU fallback below
+static bool decode_routes_to_mfma(int Hq, int Hk, int head_dim) {
+  return (head_dim == 128 || head_dim == 64) && Hq / Hk <= 8 &&
+         getenv("SUTRO_DECODE_VALU") == nullptr;
+}
+
+// Local attention (window > 0 and/or sinks != null): MFMA kernel only.
+// Returns 0, or -1 (nothing launched) where the router would pick the VALU
+// kernel, which has neither: the caller raises.
+extern "C" int sutro_attn_decode_local(void* out, const void* q,
+                                       const void* k_cache,
+                                       const void* v_cache,
+                                       const int* block_tables,
+                                       const int* seq_lens, int bt_stride,
+                                       int n_dec, int Hq, int Hk, int head_dim,
+                                       int kv_fp8, int seq_offset, float scale,
+                                       int window, const float* sinks,
+                                       hipStream_t s) {
+  if (!decode_routes_to_mfma(Hq, Hk, head_dim)) return -1;
+  if (n_dec == 0) return 0;
+  sutro_attn_decode_mfma_local(out, q, k_cache, v_cache, block_tables,
+                               seq_lens, bt_stride, n_dec, Hq, Hk, seq_offset,
+                               scale, kv_fp8, head_dim, window, sinks, s);
+  return 0;
+}
+
 extern "C" void sutro_attn_decode(void* out, const void* q, const void* k_cache,
                                   const void* v_cache, const int* block_tables,
                                   const int* seq_lens, int bt_stride, int n_dec,
@@ -379,8 +412,7 @@ extern "C" void sutro_attn_decode(void* out, const void* q, const void* k_cache,
   // alpha-rescale fix (attn_decode_mfma.h, mfma_page_update) — verified against the fp32
   // reference by test_attn_head_dim_64 on hardware.
   // SUTRO_DECODE_VALU=1 falls back to the VALU kernel for A/B.
-  if ((head_dim == 128 || head_dim == 64) && Hq / Hk <= 8 &&
-      getenv("SUTRO_DECODE_VALU") == nullptr) {
+  if (decode_routes_to_mfma(Hq, Hk, head_dim)) {
     sutro_attn_decode_mfma(out, q, k_cache, v_cache, block_tables, seq_lens,
                            bt_stride, n_dec, Hq, Hk, seq_offset, scale, kv_fp8,
                            head_dim, s);

@@ -95,11 +95,15 @@ __device__ __forceinline__ void mfma_load_k(bf16frag (&ka)[2][D / 32],
 // l_run for column lo16; acc = O[column hi4*4+r][d lo16 + 16*b]) is updated
 // in place. The caller runs wave_lds_sync() between staging `qt` and the
 // first call; `vt` is covered by the sync inside.
-template <int D>
+// LOWER (local attention): positions below `lo` are masked the way positions
+// >= `valid` are. The mask is a select on the score, so a page with lo <= 0
+// runs the arithmetic of the LOWER = false body; without the flag the
+// comparison is not compiled and the body is the shared-prefix kernel's.
+template <int D, bool LOWER = false>
 __device__ __forceinline__ void mfma_page_update(
     const u16* qt, const u16* vt, u16* p, float* alpha,
     const bf16frag (&ka)[2][D / 32], int valid, int lo16, int hi4,
-    float& m_run, float& l_run, f32x4 (&acc)[D / 16]) {
+    float& m_run, float& l_run, f32x4 (&acc)[D / 16], int lo = 0) {
   constexpr int DB = D / 16;
   // ---- QK^T via MFMA: two 16-position halves
   f32x4 s01[2];
@@ -125,6 +129,8 @@ __device__ __forceinline__ void mfma_page_update(
       const int pos = half * 16 + hi4 * 4 + r;
       float x = s01[half][r];
       if (pos >= valid) x = -1e30f;
+      if constexpr (LOWER)
+        if (pos < lo) x = -1e30f;
       sv[half * 4 + r] = x;
     }
   float tmax = sv[0];

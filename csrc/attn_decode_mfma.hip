@@ -33,7 +33,13 @@ struct MfmaSmem {
 // CONT (shared-prefix decode, attn_decode_prefix.hip): a row with
 // row_prefix_pages[row] = P > 0 resumes from the f32 softmax state the
 // partial kernel left for its first P pages and starts its page loop at P.
-template <int D, bool KV8, bool CONT = false>
+// LOCAL (local attention; never together with CONT): `window` W > 0 keeps the
+// last W positions, so the page loop starts at page max(0, L - W) / 32 and
+// that page masks the positions below L - W; `sinks` (f32 [Hq], or null)
+// seeds head h's softmax state with m = sinks[h], l = 1, O = 0: one more
+// logit in the denominator that adds nothing to the output. Without the flag
+// neither argument is read and the kernel is the one it was before them.
+template <int D, bool KV8, bool CONT = false, bool LOCAL = false>
 __global__ __launch_bounds__(256) void attn_decode_mfma_kernel(
     u16* __restrict__ out,            // [n_dec, Hq, D]
     const u16* __restrict__ q,        // [n_dec, Hq, D]
@@ -45,7 +51,10 @@ __global__ __launch_bounds__(256) void attn_decode_mfma_kernel(
     const int* __restrict__ row_prefix_pages = nullptr,  // [n_dec] (CONT)
     const float* __restrict__ part_o = nullptr,          // [n_dec, Hq, D]
     const float* __restrict__ part_m = nullptr,          // [n_dec, Hq]
-    const float* __restrict__ part_l = nullptr) {
+    const float* __restrict__ part_l = nullptr,
+    int window = 0,                                      // (LOCAL)
+    const float* __restrict__ sinks = nullptr) {         // [Hq] (LOCAL)
+  static_assert(!(CONT && LOCAL), "the shared-prefix resume takes no window");
   const int lane = threadIdx.x & (WAVE - 1);
   const int wid = threadIdx.x / WAVE;
   const long item = (long)blockIdx.x * (blockDim.x / WAVE) + wid;
@@ -109,6 +118,16 @@ __global__ __launch_bounds__(256) void attn_decode_mfma_kernel(
     }
   }
 
+  int first_pos = 0;   // first visible position (LOCAL)
+  if constexpr (LOCAL) {
+    if (window > 0) first_pos = max(0, L - window);
+    pg0 = first_pos / BS;   // holds position L - 1 at the latest: pg0 < npages
+    if (sinks != nullptr && lo16 < G) {
+      m_run = sinks[kh * G + lo16];
+      l_run = 1.f;
+    }
+  }
+
   constexpr int ES = KV8 ? 1 : 2;  // bytes per cache element
   for (int pg = pg0; pg < npages; ++pg) {
     const long kv_base = (((long)bt[pg] * Hk + kh) * BS) * D * ES;
@@ -117,8 +136,9 @@ __global__ __launch_bounds__(256) void attn_decode_mfma_kernel(
     mfma_stage_vt<D, KV8>(sm->vt, v_cache + kv_base, lane);
     bf16frag ka[2][D / 32];
     mfma_load_k<D, KV8>(ka, k_cache + kv_base, lo16, hi4);
-    mfma_page_update<D>(sm->qt, sm->vt, sm->p, sm->alpha, ka, valid, lo16,
-                        hi4, m_run, l_run, acc);
+    mfma_page_update<D, LOCAL>(sm->qt, sm->vt, sm->p, sm->alpha, ka, valid,
+                               lo16, hi4, m_run, l_run, acc,
+                               first_pos - pg * BS);
   }
 
   // ---- epilogue: divide rows by their head's l and scatter
@@ -137,8 +157,9 @@ __global__ __launch_bounds__(256) void attn_decode_mfma_kernel(
   }
 }
 
-// CONT: the shared-prefix route passes the partial-state buffers
-template <bool CONT>
+// CONT: the shared-prefix route passes the partial-state buffers;
+// LOCAL: the local-attention route passes a window and/or sinks
+template <bool CONT, bool LOCAL = false>
 static void launch_decode_mfma(void* out, const void* q, const void* k_cache,
                                const void* v_cache, const int* block_tables,
                                const int* seq_lens, int bt_stride, int n_dec,
@@ -146,7 +167,8 @@ static void launch_decode_mfma(void* out, const void* q, const void* k_cache,
                                int kv_fp8, int head_dim,
                                const int* row_prefix_pages,
                                const float* part_o, const float* part_m,
-                               const float* part_l, hipStream_t s) {
+                               const float* part_l, hipStream_t s,
+                               int window = 0, const float* sinks = nullptr) {
   // 2 waves/block (bf16 D=128: 31.4 KB LDS -> 5 blocks/CU)
   static const char* wpb_env = getenv("SUTRO_DECODE_WPB");
   const int wpb = wpb_env ? atoi(wpb_env) : 2;
@@ -154,13 +176,14 @@ static void launch_decode_mfma(void* out, const void* q, const void* k_cache,
   const long blocks = (items + wpb - 1) / wpb;
 #define LAUNCH_MFMA(D, KV8)                                                  \
   if (head_dim == D && kv_fp8 == (KV8 ? 1 : 0)) {                            \
-    hipLaunchKernelGGL((attn_decode_mfma_kernel<D, KV8, CONT>),              \
+    hipLaunchKernelGGL((attn_decode_mfma_kernel<D, KV8, CONT, LOCAL>),       \
                        dim3((unsigned)blocks), dim3(wpb * WAVE),             \
                        sizeof(MfmaSmem<D>) * wpb, s, (u16*)out,              \
                        (const u16*)q, (const u8*)k_cache,                    \
                        (const u8*)v_cache, block_tables, seq_lens,           \
                        bt_stride, n_dec, Hq, Hk, seq_offset, scale,          \
-                       row_prefix_pages, part_o, part_m, part_l);            \
+                       row_prefix_pages, part_o, part_m, part_l, window,     \
+                       sinks);                                               \
     return;                                                                  \
   }
   LAUNCH_MFMA(128, false)
@@ -182,6 +205,18 @@ extern "C" void sutro_attn_decode_mfma(void* out, const void* q,
                             bt_stride, n_dec, Hq, Hk, seq_offset, scale,
                             kv_fp8, head_dim, nullptr, nullptr, nullptr,
                             nullptr, s);
+}
+
+// local attention: window > 0 and/or sinks != null (either may be neutral)
+extern "C" void sutro_attn_decode_mfma_local(
+    void* out, const void* q, const void* k_cache, const void* v_cache,
+    const int* block_tables, const int* seq_lens, int bt_stride, int n_dec,
+    int Hq, int Hk, int seq_offset, float scale, int kv_fp8, int head_dim,
+    int window, const float* sinks, hipStream_t s) {
+  launch_decode_mfma<false, true>(out, q, k_cache, v_cache, block_tables,
+                                  seq_lens, bt_stride, n_dec, Hq, Hk,
+                                  seq_offset, scale, kv_fp8, head_dim, nullptr,
+                                  nullptr, nullptr, nullptr, s, window, sinks);
 }
 
 // per-row kernel resuming from the partial kernel's state (decode-only batch:

@@ -48,7 +48,14 @@ struct PrefillSmem {
 
 #define PWAVE_ELEMS (QTILE * VT_PAD)  // P tile per wave (bf16)
 
-template <int D, bool KV8>
+// LOCAL (local attention): `window` W > 0 lets the query at position i see
+// keys i - W < j <= i, so the page loop starts at the page holding row 0's
+// window start; `sinks` (f32 [Hq], or null) seeds each row's softmax state
+// with m = sinks[head], l = 1. Rows further down the tile start later than
+// row 0, so a walked page can be fully masked for them while their state is
+// still m = -1e30: a masked score's weight is set to 0, not computed as
+// exp(-1e30 - m). Without the flag the kernel is the one it was before.
+template <int D, bool KV8, bool LOCAL = false>
 __global__ void attn_prefill_kernel(
     u16* __restrict__ out,            // [T, Hq, D]
     const u16* __restrict__ q,        // [T, Hq, D]
@@ -59,7 +66,9 @@ __global__ void attn_prefill_kernel(
     const int* __restrict__ qlocs,         // [S+1]
     const int* __restrict__ tile_seq,      // [n_tiles]
     const int* __restrict__ tile_q0,       // [n_tiles]
-    int bt_stride, int Hq, int Hk, float scale) {
+    int bt_stride, int Hq, int Hk, float scale,
+    int window = 0,                        // (LOCAL)
+    const float* __restrict__ sinks = nullptr) {  // [Hq] (LOCAL)
   const int lane = threadIdx.x & (WAVE - 1);
   const int w = threadIdx.x / WAVE;      // wave id == q-head within group
   const int G = blockDim.x / WAVE;
@@ -103,8 +112,16 @@ __global__ void attn_prefill_kernel(
 #pragma unroll
   for (int b = 0; b < D / 32; ++b) acc_o[b] = (f32x16)(0.f);
   float m_run = -1e30f, l_run = 0.f;
+  int kt0 = 0;
+  if constexpr (LOCAL) {
+    if (window > 0) kt0 = max(0, qabs_base - window + 1) / BS;
+    if (sinks != nullptr) {
+      m_run = sinks[hq];
+      l_run = 1.f;
+    }
+  }
 
-  for (int kt = 0; kt < ntiles_kv; ++kt) {
+  for (int kt = kt0; kt < ntiles_kv; ++kt) {
     const int blk = block_tables[(long)s * bt_stride + kt];
     const long kv_base = (((long)blk * Hk + kh) * BS) * D;  // in elements
     const int kv0 = kt * BS;
@@ -171,11 +188,15 @@ __global__ void attn_prefill_kernel(
     float sc[16];
     float tmax = -1e30f;
     const int qabs = qabs_base + my_q;
+    // first visible key of this row (LOCAL)
+    const int klo = (LOCAL && window > 0) ? qabs - window + 1 : 0;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int kvpos = kv0 + d_row(r, hi);
       float v = d1[r] * scale;
       if (kvpos > qabs || kvpos >= L) v = -1e30f;
+      if constexpr (LOCAL)
+        if (kvpos < klo) v = -1e30f;
       sc[r] = v;
       tmax = fmaxf(tmax, v);
     }
@@ -185,7 +206,13 @@ __global__ void attn_prefill_kernel(
     float psum = 0.f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const float p = __expf(sc[r] - m_new);
+      float p = __expf(sc[r] - m_new);
+      if constexpr (LOCAL) {
+        // a masked key weighs exactly 0 even where the whole page is masked
+        // and m_new is still -1e30 (exp(0) = 1 otherwise)
+        const int kvpos = kv0 + d_row(r, hi);
+        if (kvpos > qabs || kvpos >= L || kvpos < klo) p = 0.f;
+      }
       sc[r] = p;
       psum += p;
     }
@@ -621,6 +648,13 @@ extern "C" int sutro_attn_prefill_pipe_supported(int Hq, int Hk, int head_dim,
 // with tile lists built at a step of tile_rows. Returns 0; -1 for a
 // configuration the chosen kernel does not take (nothing is launched); -2
 // if the pipelined kernel's LDS size was refused or its launch failed.
+extern "C" int sutro_attn_prefill_local(void*, const void*, const void*,
+                                        const void*, const int*, const int*,
+                                        const int*, const int*, const int*,
+                                        int, int, int, int, int, int, float,
+                                        int, int, int, const float*,
+                                        hipStream_t);
+
 extern "C" int sutro_attn_prefill(void* out, const void* q,
                                   const void* k_cache, const void* v_cache,
                                   const int* block_tables,
@@ -629,7 +663,30 @@ extern "C" int sutro_attn_prefill(void* out, const void* q,
                                   int n_tiles, int bt_stride, int Hq, int Hk,
                                   int head_dim, int kv_fp8, float scale,
                                   int tile_rows, int variant, hipStream_t s) {
+  return sutro_attn_prefill_local(out, q, k_cache, v_cache, block_tables,
+                                  seq_lens, qlocs, tile_seq, tile_q0, n_tiles,
+                                  bt_stride, Hq, Hk, head_dim, kv_fp8, scale,
+                                  tile_rows, variant, 0, nullptr, s);
+}
+
+// The same with local attention: window > 0 and/or sinks != null run the
+// reference kernel's LOCAL instantiation whatever `variant` says (the
+// pipelined kernel has neither), so tile lists must be built at 32 rows:
+// -1 otherwise. window == 0 and sinks == null is sutro_attn_prefill.
+extern "C" int sutro_attn_prefill_local(void* out, const void* q,
+                                        const void* k_cache,
+                                        const void* v_cache,
+                                        const int* block_tables,
+                                        const int* seq_lens, const int* qlocs,
+                                        const int* tile_seq,
+                                        const int* tile_q0, int n_tiles,
+                                        int bt_stride, int Hq, int Hk,
+                                        int head_dim, int kv_fp8, float scale,
+                                        int tile_rows, int variant, int window,
+                                        const float* sinks, hipStream_t s) {
   const int G = Hq / Hk;
+  const bool local = window > 0 || sinks != nullptr;
+  if (local) variant = 0;
   if (variant == 0) {
     if (tile_rows != QTILE) return -1;
   } else if (!sutro_attn_prefill_pipe_supported(Hq, Hk, head_dim, tile_rows)) {
@@ -637,16 +694,19 @@ extern "C" int sutro_attn_prefill(void* out, const void* q,
   }
   if (n_tiles == 0) return 0;
   int rc = 0;
+#define LAUNCH_PF_L(DV, KV, LOC)                                              \
+  hipLaunchKernelGGL((attn_prefill_kernel<DV, KV, LOC>), dim3(n_tiles, Hk),   \
+                     dim3(G * WAVE), smem, s, (u16*)out, (const u16*)q,       \
+                     (const u8*)k_cache, (const u8*)v_cache, block_tables,    \
+                     seq_lens, qlocs, tile_seq, tile_q0, bt_stride, Hq, Hk,   \
+                     scale, window, sinks)
 #define LAUNCH_PF(DV, KV)                                                     \
   do {                                                                        \
     const size_t smem = sizeof(PrefillSmem<DV>) +                             \
                         (size_t)G * PWAVE_ELEMS * sizeof(u16) +               \
                         (size_t)G * 2 * QTILE * sizeof(float);                \
-    hipLaunchKernelGGL((attn_prefill_kernel<DV, KV>), dim3(n_tiles, Hk),      \
-                       dim3(G * WAVE), smem, s, (u16*)out, (const u16*)q,     \
-                       (const u8*)k_cache, (const u8*)v_cache, block_tables,  \
-                       seq_lens, qlocs, tile_seq, tile_q0, bt_stride, Hq, Hk, \
-                       scale);                                                \
+    if (local) LAUNCH_PF_L(DV, KV, true);                                     \
+    else       LAUNCH_PF_L(DV, KV, false);                                    \
   } while (0)
 #define LAUNCH_PIPE(DV, KV, NWV, SUBSV)                                       \
   do {                                                                        \
@@ -696,6 +756,7 @@ extern "C" int sutro_attn_prefill(void* out, const void* q,
 #undef PIPE_NW
 #undef LAUNCH_PIPE
 #undef LAUNCH_PF
+#undef LAUNCH_PF_L
   return rc;
 }
 

@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <c10/hip/HIPStream.h>
 
+#include <climits>
+
 #define CHECK_CUDA(x) TORCH_CHECK((x).is_cuda(), #x " must be a GPU tensor")
 #define CHECK_CONTIG(x) TORCH_CHECK((x).is_contiguous(), #x " must be contiguous")
 #define CHECK_BF16(x) \
@@ -36,6 +38,13 @@ int sutro_attn_prefill(void*, const void*, const void*, const void*,
                        const int*, const int*, const int*, const int*,
                        const int*, int, int, int, int, int, int, float, int,
                        int, hipStream_t);
+int sutro_attn_decode_local(void*, const void*, const void*, const void*,
+                            const int*, const int*, int, int, int, int, int,
+                            int, int, float, int, const float*, hipStream_t);
+int sutro_attn_prefill_local(void*, const void*, const void*, const void*,
+                             const int*, const int*, const int*, const int*,
+                             const int*, int, int, int, int, int, int, float,
+                             int, int, int, const float*, hipStream_t);
 int sutro_attn_prefill_pipe_supported(int, int, int, int);
 void sutro_attn_decode_shared(void*, const void*, const void*, const void*,
                               const int*, const int*, int, int, int, int,
@@ -143,7 +152,8 @@ void paged_attention(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
                      torch::Tensor seq_lens, torch::Tensor qlocs, double scale,
                      int64_t num_decodes, torch::Tensor tile_seq,
                      torch::Tensor tile_q0, int64_t prefill_token_count,
-                     int64_t tile_rows, int64_t prefill_variant) {
+                     int64_t tile_rows, int64_t prefill_variant,
+                     int64_t window, c10::optional<torch::Tensor> sinks) {
   CHECK_CUDA(q); CHECK_CONTIG(q); CHECK_BF16(q); CHECK_CONTIG(k_cache);
   const int Hq = q.size(1), D = q.size(2);
   const int Hk = k_cache.size(1);
@@ -154,9 +164,38 @@ void paged_attention(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
   TORCH_CHECK(bs == 32, "attention kernels require kv_block_size 32");
   TORCH_CHECK(Hq % Hk == 0 && Hq / Hk <= 8,
               "GQA group size must divide and be <= 8");
+  // local attention: a window of `window` keys (0 = none) and/or one sink
+  // logit per q head; either makes both kernels take their LOCAL route
+  TORCH_CHECK(window >= 0 && window <= INT_MAX,
+              "window must be >= 0 (got ", window, ")");
+  const float* sinks_p = nullptr;
+  if (sinks.has_value()) {
+    const torch::Tensor& sk = *sinks;
+    TORCH_CHECK(sk.is_cuda() && sk.device() == q.device(),
+                "sinks must be on q's device");
+    TORCH_CHECK(sk.scalar_type() == at::kFloat, "sinks must be f32");
+    TORCH_CHECK(sk.is_contiguous(), "sinks must be contiguous");
+    TORCH_CHECK(sk.numel() == Hq, "sinks must have one entry per q head (",
+                Hq, "), got ", sk.numel());
+    sinks_p = sk.data_ptr<float>();
+  }
+  const bool local = window > 0 || sinks_p != nullptr;
   const int bt_stride = block_tables.size(1);
   const int n_tiles = tile_seq.numel();
-  if (n_tiles > 0) {
+  if (n_tiles > 0 && local) {
+    TORCH_CHECK(tile_rows == 32, "prefill attention with a window or sinks "
+                "runs the reference kernel: build the tile lists at 32 rows "
+                "(got tile_rows ", tile_rows, ")");
+    const int rc = sutro_attn_prefill_local(
+        out.data_ptr(), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+        block_tables.data_ptr<int>(), seq_lens.data_ptr<int>(),
+        qlocs.data_ptr<int>(), tile_seq.data_ptr<int>(),
+        tile_q0.data_ptr<int>(), n_tiles, bt_stride, Hq, Hk, D,
+        is_fp8(k_cache) ? 1 : 0, (float)scale, (int)tile_rows, 0,
+        (int)window, sinks_p, cur_stream());
+    TORCH_CHECK(rc == 0, "prefill attention (window/sinks) refused Hq ", Hq,
+                ", Hk ", Hk, ", head_dim ", D);
+  } else if (n_tiles > 0) {
     // prefill_variant 0: the one-tile-per-block kernel (32-row tiles);
     // 1: the pipelined kernel, tile lists built at a step of tile_rows
     const int rc = sutro_attn_prefill(
@@ -177,6 +216,18 @@ void paged_attention(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
     const int seq_offset = S - (int)num_decodes;
     const u_int16_t* qp = (const u_int16_t*)q.data_ptr();
     u_int16_t* op = (u_int16_t*)out.data_ptr();
+    if (local) {
+      const int rc = sutro_attn_decode_local(
+          op + dec_off * Hq * D, qp + dec_off * Hq * D, k_cache.data_ptr(),
+          v_cache.data_ptr(), block_tables.data_ptr<int>(),
+          seq_lens.data_ptr<int>(), bt_stride, (int)num_decodes, Hq, Hk, D,
+          is_fp8(k_cache) ? 1 : 0, seq_offset, (float)scale, (int)window,
+          sinks_p, cur_stream());
+      TORCH_CHECK(rc == 0, "decode attention with a window or sinks needs "
+                  "the MFMA kernel, but SUTRO_DECODE_VALU routes this call "
+                  "to the VALU kernel, which has neither");
+      return;
+    }
     sutro_attn_decode(op + dec_off * Hq * D, qp + dec_off * Hq * D,
                       k_cache.data_ptr(), v_cache.data_ptr(),
                       block_tables.data_ptr<int>(), seq_lens.data_ptr<int>(),
@@ -773,7 +824,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("block_tables"), py::arg("seq_lens"), py::arg("qlocs"),
         py::arg("scale"), py::arg("num_decodes"), py::arg("tile_seq"),
         py::arg("tile_q0"), py::arg("prefill_token_count"),
-        py::arg("tile_rows") = 32, py::arg("prefill_variant") = 0);
+        py::arg("tile_rows") = 32, py::arg("prefill_variant") = 0,
+        py::arg("window") = 0, py::arg("sinks") = py::none());
   m.def("attn_prefill_pipe_supported",
         [](int64_t hq, int64_t hk, int64_t d, int64_t rows) {
           return sutro_attn_prefill_pipe_supported((int)hq, (int)hk, (int)d,

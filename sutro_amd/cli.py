@@ -195,8 +195,11 @@ def models():
               type=click.Choice(["bf16", "fp8_e4m3"]),
               help="storage of the dense projections (qkv, o, gate_up, down; "
                    "fp8_e4m3 halves them and runs them W8A8)")
+@click.option("--local-attention", is_flag=True, default=False,
+              help="run sliding-window layers with their window and "
+                   "attention sinks where the model has them (gpt-oss)")
 def serve(host: str, port: int, device: str, moe_weight_dtype: str,
-          dense_weight_dtype: str):
+          dense_weight_dtype: str, local_attention: bool):
     """Serve the HTTP API (the same endpoint contract as api.sutro.sh)."""
     from .service.http_api import run_server
 
@@ -205,6 +208,8 @@ def serve(host: str, port: int, device: str, moe_weight_dtype: str,
         engine_kwargs["moe_weight_dtype"] = moe_weight_dtype
     if dense_weight_dtype != "bf16":
         engine_kwargs["dense_weight_dtype"] = dense_weight_dtype
+    if local_attention:
+        engine_kwargs["local_attention"] = True
     engine_kwargs = engine_kwargs or None
     run_server(host=host, port=port, device=device,
                engine_kwargs=engine_kwargs)

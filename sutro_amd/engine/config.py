@@ -86,12 +86,33 @@ class EngineConfig:
     # per-row kernel for the rest — bit-identical output. Meaningful only
     # with enable_prefix_caching on the GPU MFMA decode route.
     prefix_decode: str = "per_row"
+    # local attention: run the spec's sliding-window layers with their window
+    # and its attention sinks (ModelSpec.sliding_window /
+    # sliding_window_pattern / attention_sinks; docs/ENGINE.md, "Local
+    # attention"). Off: those fields are ignored and every layer is full
+    # causal attention without a sinks parameter, as before. Ignored for
+    # specs with neither (a service hands one engine_kwargs to every model).
+    local_attention: bool = False
 
     def __post_init__(self) -> None:
         if self.prefix_decode not in ("per_row", "shared"):
             raise ValueError(
                 f"prefix_decode must be 'per_row' or 'shared', "
                 f"got {self.prefix_decode!r}")
+        if not isinstance(self.local_attention, bool):
+            raise ValueError(
+                f"local_attention must be True or False, "
+                f"got {self.local_attention!r}")
+        if self.local_attention and (
+                self.spec.sliding_window < 0
+                or self.spec.sliding_window_pattern < 0
+                or (self.spec.sliding_window_pattern > 0
+                    and self.spec.sliding_window == 0)):
+            raise ValueError(
+                f"local_attention needs sliding_window > 0 where "
+                f"sliding_window_pattern > 0, and neither negative (got "
+                f"window {self.spec.sliding_window}, pattern "
+                f"{self.spec.sliding_window_pattern})")
         if self.spec.embedding:
             self.enable_prefix_caching = False
         if self.moe_weight_dtype not in ("bf16", "fp8_e4m3", "mxfp4"):

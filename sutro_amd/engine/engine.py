@@ -86,7 +86,8 @@ class LLMEngine:
         if model is None:
             with torch.device(cfg.device):
                 model = Qwen3Model(self.spec, cfg.dtype, cfg.max_model_len,
-                                   self.tp, moe_ep=cfg.moe_ep)
+                                   self.tp, moe_ep=cfg.moe_ep,
+                                   local_attention=cfg.local_attention)
             if cfg.weights_path:
                 from ..models.loader import load_weights
 
@@ -95,6 +96,10 @@ class LLMEngine:
             else:
                 model.init_random_weights(cfg.seed)
         self.model = model.to(cfg.device).eval()
+        # a layer with a window or sinks exists: prefill tile lists are built
+        # at 32 rows and shared-prefix decode is off (below)
+        self.local_attention = bool(getattr(self.model, "local_attention",
+                                            False))
         if cfg.moe_weight_dtype != "bf16" and self.spec.num_experts > 0:
             from ..models.qwen3 import Qwen3MoE
 
@@ -171,7 +176,19 @@ class LLMEngine:
         self.prefix_shared = False
         self.prefix_tile_steps = 0   # decode steps that ran a non-empty tile
         self._prefix_partials = None
+        self.prefix_decode_fallback: Optional[str] = None
         if (cfg.prefix_decode == "shared" and cfg.enable_prefix_caching
+                and self.local_attention):
+            import warnings
+
+            # the partial kernel covers a tile's whole common prefix, which is
+            # wrong for a row whose window starts inside or past it; block-
+            # hash reuse itself stays on (the cache holds every position)
+            self.prefix_decode_fallback = (
+                "prefix_decode='shared' does not take local attention (a "
+                "sliding window or attention sinks); running 'per_row'")
+            warnings.warn(self.prefix_decode_fallback)
+        elif (cfg.prefix_decode == "shared" and cfg.enable_prefix_caching
                 and cfg.device.startswith("cuda")):
             from .. import ops
 
@@ -338,7 +355,8 @@ class LLMEngine:
         from .. import ops
         tile_step = ops.prefill_tile_step(
             *self.local_heads(), self.spec.head_dim,
-            max(sb.num_new_tokens[:sb.num_prefills], default=0))
+            max(sb.num_new_tokens[:sb.num_prefills], default=0),
+            local_attention=self.local_attention)
         tiles_s: List[int] = []
         tiles_q0: List[int] = []
         for s in range(sb.num_prefills):

@@ -47,8 +47,9 @@ class PrefillGraphRunner:
         self.tile_max = self.s_max + self.t_pad // 32
         # rows per prefill q tile of the routed attention kernel
         from .. import ops
-        self.tile_step = ops.prefill_tile_step(*engine.local_heads(),
-                                               engine.spec.head_dim)
+        self.tile_step = ops.prefill_tile_step(
+            *engine.local_heads(), engine.spec.head_dim,
+            local_attention=engine.local_attention)
         # replay only when the wave is big enough that padding waste is small
         self.min_tokens = cfg.graph_prefill_min_tokens
         self._h2d_done = (torch.cuda.Event()
@@ -115,8 +116,9 @@ class PrefillGraphRunner:
         # the wave runs eager
         from .. import ops
         eng = self.engine
-        if ops.prefill_tile_step(*eng.local_heads(),
-                                 eng.spec.head_dim) != self.tile_step:
+        if ops.prefill_tile_step(
+                *eng.local_heads(), eng.spec.head_dim,
+                local_attention=eng.local_attention) != self.tile_step:
             return False
         return (self.graph is not None
                 and sb.num_prefills == len(sb.reqs)

@@ -18,6 +18,13 @@ experts as the uint8 pair `<...>.mlp.gate_up_blocks` / `.gate_up_scales` and
 moe_weight_dtype="mxfp4")` copies such a pair into the model bit for bit,
 without a bf16 stage. The pair must have the shape of the local shard (it is
 not re-sliced for TP/EP). The published gpt-oss tensor names are not mapped.
+
+Attention sinks (`EngineConfig.local_attention` with a spec that has them):
+the parameter is `layers.N.self_attn.sinks`, f32 [num_heads], the name gpt-oss
+checkpoints use (`model.layers.N.self_attn.sinks`); it is sliced with the q
+heads under TP and is required under strict=True. A model built without sinks
+has no such parameter, so a checkpoint that carries them reports the tensors
+as unexpected (strict=True) or skips them (strict=False), like any other.
 """
 
 from __future__ import annotations
@@ -175,7 +182,7 @@ def load_weights(model: torch.nn.Module, path: str, strict: bool = True,
             f"parameter (strict=True): {unexpected[:6]}"
             f"{'...' if len(unexpected) > 6 else ''}")
     missing = [n for n, p in params.items()
-               if n not in loaded and p.dim() >= 2]
+               if n not in loaded and (p.dim() >= 2 or n.endswith(".sinks"))]
     if missing and strict:
         raise ValueError(f"checkpoint missing parameters: {missing[:8]}"
                          f"{'...' if len(missing) > 8 else ''}")

@@ -91,7 +91,8 @@ class RMSNorm(nn.Module):
 
 class Qwen3Attention(nn.Module):
     def __init__(self, spec: ModelSpec, dtype: torch.dtype, layer_idx: int,
-                 tp: Optional[TPContext] = None):
+                 tp: Optional[TPContext] = None,
+                 local_attention: bool = False):
         super().__init__()
         tp = tp or TPContext()
         self.tp = tp
@@ -121,6 +122,15 @@ class Qwen3Attention(nn.Module):
         if spec.qk_norm:
             self.q_norm = RMSNorm(self.head_dim, spec.rms_eps, dtype)
             self.k_norm = RMSNorm(self.head_dim, spec.rms_eps, dtype)
+        # local attention (EngineConfig.local_attention): this layer's window
+        # and one f32 sink logit per local q head, sharded with the q heads
+        self.window = spec.layer_window(layer_idx) if local_attention else 0
+        if local_attention and spec.attention_sinks:
+            self.sinks = nn.Parameter(
+                torch.zeros(self.num_heads, dtype=torch.float32))
+            _mark_shard(self.sinks, (spec.num_heads,), 0, tp)
+        else:
+            self.sinks = None
 
     @torch.no_grad()
     def quantize_dense_fp8(self) -> None:
@@ -160,7 +170,8 @@ class Qwen3Attention(nn.Module):
                                     fb.seq_lens, fb.query_start_locs, self.scale,
                                     fb.num_decodes_tail, fb.tile_seq, fb.tile_q0,
                                     fb.prefill_token_count,
-                                    tile_rows=fb.prefill_tile_rows)
+                                    tile_rows=fb.prefill_tile_rows,
+                                    window=self.window, sinks=self.sinks)
         return self.tp.all_reduce(
             _dense_linear(self.o_proj, o.view(T, self.q_size)))
 
@@ -721,10 +732,12 @@ class Qwen3MoE(nn.Module):
 
 class Qwen3Block(nn.Module):
     def __init__(self, spec: ModelSpec, dtype: torch.dtype, layer_idx: int,
-                 tp: Optional[TPContext] = None, moe_ep: bool = False):
+                 tp: Optional[TPContext] = None, moe_ep: bool = False,
+                 local_attention: bool = False):
         super().__init__()
         self.input_layernorm = RMSNorm(spec.hidden_size, spec.rms_eps, dtype)
-        self.self_attn = Qwen3Attention(spec, dtype, layer_idx, tp)
+        self.self_attn = Qwen3Attention(spec, dtype, layer_idx, tp,
+                                        local_attention)
         self.post_attention_layernorm = RMSNorm(spec.hidden_size, spec.rms_eps, dtype)
         if spec.num_experts > 0:
             self.mlp = Qwen3MoE(spec, dtype, tp, ep=moe_ep)
@@ -752,13 +765,17 @@ class Qwen3Model(nn.Module):
     specs `compute_logits` projects selected rows through it."""
 
     def __init__(self, spec: ModelSpec, dtype: torch.dtype, max_len: int,
-                 tp: Optional[TPContext] = None, moe_ep: bool = False):
+                 tp: Optional[TPContext] = None, moe_ep: bool = False,
+                 local_attention: bool = False):
         super().__init__()
         self.spec = spec
         self.tp = tp or TPContext()
+        # windows and sinks of the spec are built only when asked for
+        self.local_attention = bool(local_attention
+                                    and spec.has_local_attention)
         self.embed_tokens = nn.Embedding(spec.vocab_size, spec.hidden_size, dtype=dtype)
         self.layers = nn.ModuleList(
-            [Qwen3Block(spec, dtype, i, self.tp, moe_ep)
+            [Qwen3Block(spec, dtype, i, self.tp, moe_ep, self.local_attention)
              for i in range(spec.num_layers)]
         )
         self.norm = RMSNorm(spec.hidden_size, spec.rms_eps, dtype)
@@ -804,12 +821,15 @@ class Qwen3Model(nn.Module):
         import zlib
 
         for name, p in sorted(self.named_parameters()):
-            if p.dim() < 2:
+            sinks = name.endswith(".sinks")
+            if p.dim() < 2 and not sinks:
                 p.fill_(1.0)  # norm weights
                 continue
             full_shape = getattr(p, "_tp_full_shape", tuple(p.shape))
             fan_in = full_shape[-1] if "embed" not in name else full_shape[0]
             std = 0.02 if "embed" in name else (1.0 / math.sqrt(fan_in))
+            if sinks:
+                std = 1.0  # sink logits: score units, N(0, 1)
             dev = p.device
             gen = torch.Generator(device=dev)
             gen.manual_seed(seed * 1000003 + zlib.crc32(name.encode()))

@@ -345,11 +345,17 @@ def prefill_tile_rows(num_heads: int, num_kv_heads: int,
 
 
 def prefill_tile_step(num_heads: int, num_kv_heads: int, head_dim: int,
-                      max_new_tokens: Optional[int] = None) -> int:
+                      max_new_tokens: Optional[int] = None,
+                      local_attention: bool = False) -> int:
     """Step at which the engine builds its prefill tile lists. A batch whose
     longest chunk has at most 32 new tokens (`max_new_tokens`) is built at 32
     rows even where the layout's rule names more: the further sub-tiles of
-    every block would be empty (measured in capture A1, seeded step)."""
+    every block would be empty (measured in capture A1, seeded step).
+    `local_attention`: the model has a layer with a window or sinks; those
+    run the reference kernel, whose tiles have 32 rows, and one tile list
+    serves every layer."""
+    if local_attention:
+        return 32
     rows = prefill_tile_rows(num_heads, num_kv_heads, head_dim) or 32
     if max_new_tokens is not None and max_new_tokens <= 32:
         return 32
@@ -366,8 +372,16 @@ def paged_attention(
     prefill_token_count: int = 0,
     tile_rows: int = 32,
     prefill_variant: Optional[str] = None,
+    window: int = 0,
+    sinks: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """Attention of new tokens vs full cached KV (causal within the new chunk).
+
+    `window` W > 0: a query at position i sees keys i - W < j <= i (0: all
+    keys <= i). `sinks`: f32 [Hq], one extra softmax logit per head that adds
+    to the denominator only (torch_ref.paged_attention states both). On the
+    GPU either one routes prefill tiles to the reference kernel, so the tile
+    lists must have 32 rows, and decode rows to the MFMA kernel.
 
     `num_decodes_tail`: trailing sequences that are single-token decodes (the
     GPU path routes them to the decode kernel). `tile_seq`/`tile_q0`: int32
@@ -381,6 +395,14 @@ def paged_attention(
         if tile_seq is None:
             tile_seq = torch.empty(0, dtype=torch.int32, device=q.device)
             tile_q0 = tile_seq
+        if window < 0:
+            raise ValueError(f"window must be >= 0, got {window}")
+        if window > 0 or sinks is not None:
+            _require_hip().paged_attention(
+                out, q, k_cache, v_cache, block_tables, seq_lens,
+                query_start_locs, scale, num_decodes_tail, tile_seq, tile_q0,
+                prefill_token_count, tile_rows, 0, window, sinks)
+            return out
         if prefill_variant is None:
             pipe = (tile_rows != 32 or prefill_tile_rows(
                 q.shape[1], k_cache.shape[1], q.shape[2]) is not None)
@@ -395,7 +417,8 @@ def paged_attention(
                                        1 if pipe else 0)
         return out
     return torch_ref.paged_attention(q, k_cache, v_cache, block_tables,
-                                     seq_lens, query_start_locs, scale)
+                                     seq_lens, query_start_locs, scale,
+                                     window=window, sinks=sinks)
 
 
 PREFIX_CB = 4  # column blocks per wave of attn_prefix_partial_kernel

@@ -78,11 +78,24 @@ def paged_attention(
     seq_lens: torch.Tensor,          # [S] total length incl. this step's tokens
     query_start_locs: torch.Tensor,  # [S+1] cu-seqlens of new tokens
     scale: float,
+    window: int = 0,
+    sinks: torch.Tensor | None = None,
 ) -> torch.Tensor:
     """Causal attention of each seq's new tokens against its full cached KV.
 
     New tokens MUST already be written to the cache (write_kv_cache first).
+
+    `window` W > 0 (local attention): the query at absolute position i sees
+    key j iff i - W < j <= i, i.e. W keys including its own; 0 is no window.
+    `sinks` (f32 [Hq]): head h's softmax runs over the visible scores plus
+    one extra logit sinks[h] (score units, not multiplied by `scale`) that
+    adds to the denominator and nothing to the output.
     """
+    if window < 0:
+        raise ValueError(f"window must be >= 0, got {window}")
+    if sinks is not None and sinks.numel() != q.shape[1]:
+        raise ValueError(f"sinks must have one entry per q head "
+                         f"({q.shape[1]}), got {sinks.numel()}")
     T, hq, d = q.shape
     nb, hk, bs, _ = k_cache.shape
     group = hq // hk
@@ -108,8 +121,16 @@ def paged_attention(
         kpos = torch.arange(L, device=q.device)
         qpos = torch.arange(L - nq, L, device=q.device)
         mask = kpos.unsqueeze(0) > qpos.unsqueeze(1)  # [nq, L]
+        if window > 0:
+            mask = mask | (kpos.unsqueeze(0) <= qpos.unsqueeze(1) - window)
         scores.masked_fill_(mask.unsqueeze(0), float("-inf"))
-        probs = torch.softmax(scores, dim=-1)
+        if sinks is not None:
+            # the sink is one more logit column; its probability is dropped
+            col = sinks.float().to(q.device).view(hq, 1, 1).expand(hq, nq, 1)
+            probs = torch.softmax(torch.cat([scores, col], dim=-1),
+                                  dim=-1)[..., :L]
+        else:
+            probs = torch.softmax(scores, dim=-1)
         o = torch.einsum("hqk,hkd->hqd", probs, vh)   # [hq, nq, d]
         out[q0:q1] = o.transpose(0, 1).to(out.dtype)
     return out
