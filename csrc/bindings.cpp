@@ -86,6 +86,12 @@ void sutro_quant_weight_mxfp4(void*, void*, const void*, long, int, int,
 void sutro_grouped_gemm_mxfp4(void*, const void*, const float*, const void*,
                               const void*, const int*, const int*, const int*,
                               int, int, int, long, int, int, hipStream_t);
+void sutro_quant_rows_fp8_block128(void*, float*, const void*, long, long,
+                                   long, hipStream_t);
+int sutro_gemm_tn_fp8_block_pipe_launch(void*, const void*, const float*,
+                                        long, const void*, const float*,
+                                        const void*, int, int, long, int, int,
+                                        hipStream_t);
 int sutro_gemm_tn_fp8_pipe_launch(void*, const void*, const float*,
                                   const void*, const float*, const void*, int,
                                   int, long, int, int, hipStream_t);
@@ -477,6 +483,99 @@ torch::Tensor gemm_fp8_gate_up_silu(torch::Tensor a_q, torch::Tensor a_scale,
       w_q.data_ptr(), w_scale.data_ptr<float>(), nullptr, (int)M, (int)N, Kp,
       2, (int)xcd_swz, cur_stream());
   TORCH_CHECK(e == 0, "gemm_fp8_gate_up_silu launch setup failed: ", e);
+  return out;
+}
+
+// bf16 [R, K] -> (e4m3 codes [R, K], f32 scales [K/128, R]): one scale per
+// row and group of 128 K elements, K-block-major
+// (csrc/gemm_tn_fp8_block_pipe.hip). K % 128 == 0.
+std::vector<torch::Tensor> quant_rows_fp8_block128(torch::Tensor x) {
+  CHECK_CUDA(x); CHECK_CONTIG(x); CHECK_BF16(x);
+  TORCH_CHECK(x.dim() == 2, "x must be 2-d");
+  const long R = x.size(0), K = x.size(1);
+  TORCH_CHECK(K >= 128 && K % 128 == 0,
+              "K must be a positive multiple of 128 (K=", K, ")");
+  auto q = torch::empty({R, K}, x.options().dtype(at::kFloat8_e4m3fn));
+  auto s = torch::empty({K / 128, R}, x.options().dtype(at::kFloat));
+  sutro_quant_rows_fp8_block128(q.data_ptr(), s.data_ptr<float>(),
+                                x.data_ptr(), R, K, R, cur_stream());
+  return {q, s};
+}
+
+// shared operand checks of the two block-scaled FP8 dense GEMM bindings:
+// a_q [M, K] e4m3 + a_s [K/128, M] f32 (rows may be strided), w_q [N, K]
+// e4m3 + w_s [N/128, K/128] f32
+static void check_fp8_block_gemm_args(const torch::Tensor& a_q,
+                                      const torch::Tensor& a_s,
+                                      const torch::Tensor& w_q,
+                                      const torch::Tensor& w_s) {
+  CHECK_CUDA(a_q); CHECK_CONTIG(a_q); CHECK_CUDA(w_q); CHECK_CONTIG(w_q);
+  TORCH_CHECK(is_fp8(a_q) && is_fp8(w_q), "a_q, w_q must be float8_e4m3fn");
+  CHECK_CUDA(a_s); CHECK_CUDA(w_s); CHECK_CONTIG(w_s);
+  TORCH_CHECK(a_s.scalar_type() == at::kFloat
+              && w_s.scalar_type() == at::kFloat, "scales must be f32");
+  TORCH_CHECK(a_q.dim() == 2 && w_q.dim() == 2 && a_s.dim() == 2
+              && w_s.dim() == 2, "a_q, a_s, w_q and w_s must be 2-d");
+  const long M = a_q.size(0), K = a_q.size(1), N = w_q.size(0);
+  TORCH_CHECK(w_q.size(1) == K, "K mismatch");
+  TORCH_CHECK(M >= 1 && K >= 128 && K % 128 == 0,
+              "needs M >= 1 and K a positive multiple of 128 (K=", K, ")");
+  TORCH_CHECK(N >= 128 && N % 128 == 0,
+              "N must be a positive multiple of 128 (N=", N, ")");
+  // the kernel rounds M and N up to the 256 tile in int
+  TORCH_CHECK(M <= (1L << 31) - 256 && N <= (1L << 31) - 256,
+              "M/N too large");
+  TORCH_CHECK(a_s.size(0) == K / 128 && a_s.size(1) == M,
+              "a_s must be [K/128, M]");
+  // (a dimension of size 1 carries no meaningful stride)
+  TORCH_CHECK((M == 1 || a_s.stride(1) == 1)
+              && (K == 128 || a_s.stride(0) >= M), "a_s rows must be dense");
+  TORCH_CHECK(w_s.size(0) == N / 128 && w_s.size(1) == K / 128,
+              "w_s must be [N/128, K/128]");
+}
+
+// out[M,N] bf16 = sum_kb (a_q[:, kb] @ w_q[:, kb]^T) * a_s[kb, m]
+// * w_s[n/128, kb] (+ res, added in f32 before the one rounding) on the
+// 8-phase pipelined kernel with the scales folded in per K-tile
+// (csrc/gemm_tn_fp8_block_pipe.hip). Any M >= 1, N % 128 == 0, K % 128 == 0.
+torch::Tensor gemm_fp8_block_pipelined(torch::Tensor a_q, torch::Tensor a_s,
+                                       torch::Tensor w_q, torch::Tensor w_s,
+                                       c10::optional<torch::Tensor> res,
+                                       long xcd_swz) {
+  check_fp8_block_gemm_args(a_q, a_s, w_q, w_s);
+  const long M = a_q.size(0), K = a_q.size(1), N = w_q.size(0);
+  auto out = torch::empty({M, N}, a_q.options().dtype(at::kBFloat16));
+  const void* rp = nullptr;
+  if (res.has_value()) {
+    CHECK_CUDA(*res); CHECK_BF16(*res);
+    TORCH_CHECK(res->is_contiguous() && res->dim() == 2 &&
+                res->size(0) == M && res->size(1) == N, "res shape");
+    rp = res->data_ptr();
+  }
+  const int e = sutro_gemm_tn_fp8_block_pipe_launch(
+      out.data_ptr(), a_q.data_ptr(), a_s.data_ptr<float>(),
+      K == 128 ? M : a_s.stride(0), w_q.data_ptr(), w_s.data_ptr<float>(), rp,
+      (int)M, (int)N, K, rp ? 1 : 0, (int)xcd_swz, cur_stream());
+  TORCH_CHECK(e == 0, "gemm_fp8_block_pipelined launch setup failed: ", e);
+  return out;
+}
+
+// out[M,I] = silu(g) * u, g / u the block-scaled products with the gate / up
+// rows of the merged w_q [2I, K]; f32 SwiGLU with one rounding. I % 128 == 0.
+torch::Tensor gemm_fp8_block_gate_up_silu(torch::Tensor a_q,
+                                          torch::Tensor a_s,
+                                          torch::Tensor w_q,
+                                          torch::Tensor w_s, long xcd_swz) {
+  check_fp8_block_gemm_args(a_q, a_s, w_q, w_s);
+  const long M = a_q.size(0), K = a_q.size(1), N = w_q.size(0);
+  TORCH_CHECK(N >= 256 && N % 256 == 0,
+              "gate_up rows must be 2*I with I % 128 == 0");
+  auto out = torch::empty({M, N / 2}, a_q.options().dtype(at::kBFloat16));
+  const int e = sutro_gemm_tn_fp8_block_pipe_launch(
+      out.data_ptr(), a_q.data_ptr(), a_s.data_ptr<float>(),
+      K == 128 ? M : a_s.stride(0), w_q.data_ptr(), w_s.data_ptr<float>(),
+      nullptr, (int)M, (int)N, K, 2, (int)xcd_swz, cur_stream());
+  TORCH_CHECK(e == 0, "gemm_fp8_block_gate_up_silu launch setup failed: ", e);
   return out;
 }
 
@@ -878,4 +977,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "SwiGLU fused into the pipelined e4m3 gate_up GEMM",
         py::arg("a_q"), py::arg("a_scale"), py::arg("w_q"),
         py::arg("w_scale"), py::arg("xcd_swz") = 1);
+  m.def("quant_rows_fp8_block128", &quant_rows_fp8_block128,
+        "bf16 rows -> e4m3 codes + f32 scales per group of 128 K elements",
+        py::arg("x"));
+  m.def("gemm_fp8_block_pipelined", &gemm_fp8_block_pipelined,
+        "e4m3 TN GEMM with 128x128 weight and 1x128 activation scales",
+        py::arg("a_q"), py::arg("a_s"), py::arg("w_q"), py::arg("w_s"),
+        py::arg("res") = c10::nullopt, py::arg("xcd_swz") = 1);
+  m.def("gemm_fp8_block_gate_up_silu", &gemm_fp8_block_gate_up_silu,
+        "SwiGLU fused into the block-scaled e4m3 gate_up GEMM",
+        py::arg("a_q"), py::arg("a_s"), py::arg("w_q"), py::arg("w_s"),
+        py::arg("xcd_swz") = 1);
 }

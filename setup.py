@@ -24,6 +24,7 @@ SOURCES = [
     "csrc/gemm_tn.hip",
     "csrc/gemm_tn_pipe.hip",
     "csrc/gemm_tn_fp8_pipe.hip",
+    "csrc/gemm_tn_fp8_block_pipe.hip",
     "csrc/sampler.hip",
     "csrc/grouped_gemm.hip",
     "csrc/grouped_gemm_fp8.hip",

@@ -192,9 +192,11 @@ def models():
               help="storage of MoE expert weights (fp8_e4m3 halves them, "
                    "mxfp4 stores 4.25 bits per weight)")
 @click.option("--dense-weight-dtype", default="bf16",
-              type=click.Choice(["bf16", "fp8_e4m3"]),
+              type=click.Choice(["bf16", "fp8_e4m3", "fp8_block128"]),
               help="storage of the dense projections (qkv, o, gate_up, down; "
-                   "fp8_e4m3 halves them and runs them W8A8)")
+                   "fp8_e4m3 halves them and runs them W8A8, fp8_block128 "
+                   "does so with the 128x128 block scales of the published "
+                   "FP8 checkpoints)")
 @click.option("--local-attention", is_flag=True, default=False,
               help="run sliding-window layers with their window and "
                    "attention sinks where the model has them (gpt-oss)")

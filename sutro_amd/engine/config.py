@@ -73,6 +73,12 @@ class EngineConfig:
     # (csrc/gemm_tn_fp8_pipe.hip) — halves those bytes, which frees memory
     # for KV. Embeddings / lm_head, norms, the MoE router and the experts
     # keep their storage; independent of moe_weight_dtype.
+    # "fp8_block128": the same projections as OCP e4m3 with one f32 scale per
+    # 128x128 weight block (`weight` + `weight_scale_inv`, the layout of the
+    # published block-FP8 checkpoints, which load without a bf16 stage) and
+    # activations quantised per token and 128-wide K group, on
+    # csrc/gemm_tn_fp8_block_pipe.hip. Projections that arrive unquantised
+    # are quantised after load; ones that are not whole blocks stay bf16.
     dense_weight_dtype: str = "bf16"
     # block-hash prefix cache: full blocks of computed prompt tokens are
     # indexed by (parent block, token ids) and shared between rows by
@@ -119,10 +125,11 @@ class EngineConfig:
             raise ValueError(
                 f"moe_weight_dtype must be 'bf16', 'fp8_e4m3' or 'mxfp4', "
                 f"got {self.moe_weight_dtype!r}")
-        if self.dense_weight_dtype not in ("bf16", "fp8_e4m3"):
+        if self.dense_weight_dtype not in ("bf16", "fp8_e4m3",
+                                           "fp8_block128"):
             raise ValueError(
-                f"dense_weight_dtype must be 'bf16' or 'fp8_e4m3', "
-                f"got {self.dense_weight_dtype!r}")
+                f"dense_weight_dtype must be 'bf16', 'fp8_e4m3' or "
+                f"'fp8_block128', got {self.dense_weight_dtype!r}")
         if self.device == "cpu":
             self.dtype = torch.float32
         if self.max_model_len > self.spec.max_context:

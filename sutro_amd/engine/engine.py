@@ -92,7 +92,8 @@ class LLMEngine:
                 from ..models.loader import load_weights
 
                 load_weights(model, cfg.weights_path,
-                             moe_weight_dtype=cfg.moe_weight_dtype)
+                             moe_weight_dtype=cfg.moe_weight_dtype,
+                             dense_weight_dtype=cfg.dense_weight_dtype)
             else:
                 model.init_random_weights(cfg.seed)
         self.model = model.to(cfg.device).eval()
@@ -118,6 +119,13 @@ class LLMEngine:
             self.model.quantize_dense_fp8()
             if cfg.device.startswith("cuda"):
                 # likewise for the freed bf16 projections
+                torch.cuda.empty_cache()
+        elif cfg.dense_weight_dtype == "fp8_block128":
+            # a no-op on projections a checkpoint delivered quantised; the
+            # model was still built in bf16 first, so peak memory at load is
+            # the bf16 model's
+            self.model.quantize_dense_fp8_block128()
+            if cfg.device.startswith("cuda"):
                 torch.cuda.empty_cache()
 
         num_blocks = cfg.num_kv_blocks

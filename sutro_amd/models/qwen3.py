@@ -72,8 +72,59 @@ def _quantize_linear_fp8(lin: nn.Linear) -> None:
     lin.register_buffer("weight_scale", scale)
 
 
+@torch.no_grad()
+def install_linear_fp8_block128(lin: nn.Linear, codes: torch.Tensor,
+                                scale_inv: torch.Tensor) -> None:
+    """Put a block-quantised pair on lin under the published names: `weight`
+    (e4m3 codes [N, K], a buffer) and `weight_scale_inv` (f32 [N/128, K/128],
+    one scale per 128x128 block; dequantised weight = code * scale). The
+    unquantised parameter is dropped first and the pair is copied bit for
+    bit: no dequantised copy ever exists. Used by the quantise method below
+    and by the loader for checkpoints that are already quantised."""
+    N, K = lin.out_features, lin.in_features
+    if (codes.dtype != torch.float8_e4m3fn or tuple(codes.shape) != (N, K)):
+        raise ValueError(
+            f"block-FP8 codes must be float8_e4m3fn [{N}, {K}], got "
+            f"{codes.dtype} {tuple(codes.shape)}")
+    if (scale_inv.dtype != torch.float32 or N % 128 or K % 128
+            or tuple(scale_inv.shape) != (N // 128, K // 128)):
+        raise ValueError(
+            f"block-FP8 scales must be float32 [{N}/128, {K}/128], got "
+            f"{scale_inv.dtype} {tuple(scale_inv.shape)}")
+    dev = lin.weight.device
+    lin._parameters.pop("weight", None)
+    lin._buffers.pop("weight", None)
+    lin._buffers.pop("weight_scale_inv", None)
+    lin.register_buffer("weight", codes.to(dev).contiguous())
+    lin.register_buffer("weight_scale_inv", scale_inv.to(dev).contiguous())
+
+
+@torch.no_grad()
+def _quantize_linear_fp8_block128(lin: nn.Linear) -> None:
+    """Replace lin.weight [N, K] by the block-quantised pair of
+    torch_ref.quantize_weight_fp8_block128 (`weight`, `weight_scale_inv`);
+    the unquantised tensor is released. Idempotent (a projection that
+    arrived quantised from a checkpoint is left alone); refuses a weight that
+    is neither."""
+    if getattr(lin, "weight_scale_inv", None) is not None:
+        return
+    w = lin.weight
+    if w.dtype not in (torch.bfloat16, torch.float16, torch.float32):
+        raise RuntimeError(
+            f"weight is stored as {w.dtype}; fp8_block128 needs the "
+            "unquantised weights or a block-quantised pair")
+    codes, scale_inv = torch_ref.quantize_weight_fp8_block128(
+        w.data.contiguous())
+    del w
+    install_linear_fp8_block128(lin, codes, scale_inv)
+
+
 def _dense_linear(lin: nn.Linear, x: torch.Tensor) -> torch.Tensor:
-    """lin(x), through the W8A8 kernel when lin was quantised."""
+    """lin(x), through the block-scaled kernel when lin carries
+    `weight_scale_inv`, through the W8A8 kernel when it was quantised per
+    channel."""
+    if getattr(lin, "weight_scale_inv", None) is not None:
+        return ops.linear_fp8_block128(x, lin.weight, lin.weight_scale_inv)
     if lin.weight.dtype == torch.float8_e4m3fn:
         return ops.linear_fp8(x, lin.weight, lin.weight_scale)
     return lin(x)
@@ -144,6 +195,17 @@ class Qwen3Attention(nn.Module):
             if ops.linear_fp8_qualifies(*lin.weight.shape):
                 _quantize_linear_fp8(lin)
 
+    @torch.no_grad()
+    def quantize_dense_fp8_block128(self) -> None:
+        """Store qkv_proj / o_proj as e4m3 codes + one f32 scale per 128x128
+        block (`weight`, `weight_scale_inv`, the published block-FP8 layout)
+        and run them on ops.linear_fp8_block128. Acts on the LOCAL shard
+        after TP sharding. A projection whose shape is not whole blocks
+        (N % 128, K % 128) stays as it is. Idempotent."""
+        for lin in (self.qkv_proj, self.o_proj):
+            if ops.linear_fp8_block128_qualifies(*lin.weight.shape):
+                _quantize_linear_fp8_block128(lin)
+
     def forward(self, x: torch.Tensor, fb: ForwardBatch, kv: PagedKVCache,
                 cos_sin: torch.Tensor) -> torch.Tensor:
         T = x.shape[0]
@@ -205,9 +267,27 @@ class Qwen3MLP(nn.Module):
         if ops.linear_fp8_qualifies(*self.down_proj.weight.shape):
             _quantize_linear_fp8(self.down_proj)
 
+    @torch.no_grad()
+    def quantize_dense_fp8_block128(self) -> None:
+        """Store gate_up_proj / down_proj as e4m3 codes + one f32 scale per
+        128x128 block (`weight`, `weight_scale_inv`): gate_up then runs on
+        ops.gate_up_silu_fp8_block128 (f32 SwiGLU, one rounding), down on
+        ops.linear_fp8_block128. Acts on the LOCAL shard after TP sharding;
+        the bf16 tensor of each projection is freed before the next one is
+        quantised. A projection that is not whole blocks (gate_up: I % 128,
+        down: N % 128, either: K % 128) stays as it is. Idempotent."""
+        gu = self.gate_up_proj
+        if ops.gate_up_silu_fp8_block128_qualifies(*gu.weight.shape):
+            _quantize_linear_fp8_block128(gu)
+        if ops.linear_fp8_block128_qualifies(*self.down_proj.weight.shape):
+            _quantize_linear_fp8_block128(self.down_proj)
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         gu = self.gate_up_proj
-        if gu.weight.dtype == torch.float8_e4m3fn:
+        if getattr(gu, "weight_scale_inv", None) is not None:
+            act = ops.gate_up_silu_fp8_block128(x, gu.weight,
+                                                gu.weight_scale_inv)
+        elif gu.weight.dtype == torch.float8_e4m3fn:
             act = ops.gate_up_silu_fp8(x, gu.weight, gu.weight_scale)
         else:
             act = ops.gate_up_silu(x, gu.weight)
@@ -806,6 +886,16 @@ class Qwen3Model(nn.Module):
         for mod in self.modules():
             if isinstance(mod, (Qwen3Attention, Qwen3MLP)):
                 mod.quantize_dense_fp8()
+
+    @torch.no_grad()
+    def quantize_dense_fp8_block128(self) -> None:
+        """Block-scaled FP8 dense projections (128x128 weight blocks): the
+        same projections as quantize_dense_fp8; one that arrived quantised
+        from a checkpoint is left alone, one that arrived unquantised is
+        quantised here."""
+        for mod in self.modules():
+            if isinstance(mod, (Qwen3Attention, Qwen3MLP)):
+                mod.quantize_dense_fp8_block128()
 
     @torch.no_grad()
     def compute_logits(self, hidden: torch.Tensor) -> torch.Tensor:

@@ -617,6 +617,58 @@ def gate_up_silu_fp8(x, w_q, w_scale):
     return torch_ref.gate_up_silu_fp8(x, w_q, w_scale)
 
 
+def linear_fp8_block128_qualifies(n: int, k: int) -> bool:
+    """Weight shapes [n, k] the block-scaled FP8 dense kernel takes (plain /
+    residual epilogue): whole 128x128 scale blocks."""
+    return n >= 128 and n % 128 == 0 and k >= 128 and k % 128 == 0
+
+
+def gate_up_silu_fp8_block128_qualifies(two_i: int, k: int) -> bool:
+    """Merged gate_up shapes [2I, k] the block-scaled SwiGLU epilogue takes:
+    I % 128 == 0 (gate and up rows never share a scale block)."""
+    return two_i >= 256 and two_i % 256 == 0 and k >= 128 and k % 128 == 0
+
+
+def quantize_rows_fp8_block128(x):
+    """x [R, K], K % 128 == 0 -> (e4m3 codes [R, K], f32 scales [K/128, R]):
+    one scale = amax/448 per row and group of 128 K elements, K-block-major.
+    csrc/gemm_tn_fp8_block_pipe.hip on GPU (bf16 input), torch reference on
+    CPU — bit-identical. Fresh tensors, no host sync."""
+    if _use_hip(x):
+        q, s = _require_hip().quant_rows_fp8_block128(x.contiguous())
+        return q, s
+    return torch_ref.quantize_rows_fp8_block128(x)
+
+
+def linear_fp8_block128(x, w_q, w_s, residual=None):
+    """Block-scaled dense projection: x [T, K] (bf16 on GPU) through w_q
+    [N, K] e4m3 with one f32 scale per 128x128 block, w_s [N/128, K/128]
+    (`weight`, `weight_scale_inv` of the published block-FP8 checkpoints);
+    returns [T, N] in x's dtype, optionally + residual (added in f32 before
+    the one rounding). Arithmetic: torch_ref.linear_fp8_block128. On GPU the
+    group quantiser runs as its own pass, then
+    csrc/gemm_tn_fp8_block_pipe.hip; no host sync, every tensor from the
+    caching allocator."""
+    if _use_hip(x):
+        C = _require_hip()
+        # fresh caching-allocator tensors: safe under hipGraph capture
+        x_q, x_s = C.quant_rows_fp8_block128(x.contiguous())
+        return C.gemm_fp8_block_pipelined(x_q, x_s, w_q, w_s, residual)
+    return torch_ref.linear_fp8_block128(x, w_q, w_s, residual)
+
+
+def gate_up_silu_fp8_block128(x, w_q, w_s):
+    """SwiGLU of the merged block-scaled gate_up projection (w_q [2I, K], gate
+    rows first, w_s [2I/128, K/128]): one kernel, f32 SwiGLU on the unrounded
+    products, one rounding. Arithmetic: torch_ref.gate_up_silu_fp8_block128."""
+    if _use_hip(x):
+        C = _require_hip()
+        # fresh caching-allocator tensors: safe under hipGraph capture
+        x_q, x_s = C.quant_rows_fp8_block128(x.contiguous())
+        return C.gemm_fp8_block_gate_up_silu(x_q, x_s, w_q, w_s)
+    return torch_ref.gate_up_silu_fp8_block128(x, w_q, w_s)
+
+
 def quantize_weight_mxfp4(w):
     """w [..., K] -> MXFP4 (e2m1 code pairs uint8 [..., Kp/2], e8m0 block
     scales uint8 [..., Kp/32]); the format and rule are stated in

@@ -285,6 +285,114 @@ def gate_up_silu_fp8(x, w_q, w_scale):
     return (torch.nn.functional.silu(y[:, :inter]) * y[:, inter:]).to(x.dtype)
 
 
+FP8_BLOCK = 128
+
+
+def _quantize_groups_fp8(xf, amax):
+    """The rule shared by both block quantisers: xf f32 and amax f32 (the
+    group maximum, broadcastable to xf) -> (e4m3 codes, scale), with
+    scale = amax / 448 by true division (1 when amax == 0) and
+    code = e4m3_rne(clamp(xf / scale, -448, 448)) by true division."""
+    scale = torch.where(amax > 0, amax / torch.full_like(amax, FP8_E4M3_MAX),
+                        torch.ones_like(amax))
+    q = (xf / scale).clamp(-FP8_E4M3_MAX, FP8_E4M3_MAX)
+    return q.to(torch.float8_e4m3fn), scale
+
+
+def quantize_rows_fp8_block128(x):
+    """Reference for quant_rows_fp8_block128
+    (csrc/gemm_tn_fp8_block_pipe.hip) and the CPU path: x [R, K], K % 128 ==
+    0 -> (codes [R, K] e4m3, scales [K/128, R] f32). Every group of 128
+    consecutive K elements of a row follows the rule of `quantize_rows_fp8`:
+
+        amax  = max over the group of |f32(x[r, k])|
+        scale = amax / 448            (true f32 division; 1 when amax == 0)
+        code  = e4m3_rne(clamp(f32(x) / scale, -448, 448))   (true division)
+
+    The scales are K-block-major, scales[kb, r]: the four accumulator rows of
+    a GEMM lane are then 16 contiguous bytes. The kernel follows the same
+    sequence and agrees bit for bit."""
+    R, K = x.shape
+    if K < FP8_BLOCK or K % FP8_BLOCK:
+        raise ValueError(f"K must be a positive multiple of 128 (K={K})")
+    xf = x.float().view(R, K // FP8_BLOCK, FP8_BLOCK)
+    q, scale = _quantize_groups_fp8(xf, xf.abs().amax(dim=2, keepdim=True))
+    return q.view(R, K), scale.view(R, K // FP8_BLOCK).t().contiguous()
+
+
+def quantize_weight_fp8_block128(w):
+    """w [N, K], N % 128 == 0 and K % 128 == 0 -> (codes [N, K] e4m3,
+    scale_inv [N/128, K/128] f32): one scale per 128x128 block by the rule of
+    `quantize_rows_fp8_block128` with amax taken over the block. This is the
+    layout of the published block-FP8 checkpoints (`weight`,
+    `weight_scale_inv`): dequantised weight = code * scale_inv[n // 128,
+    k // 128]. Runs once at start-up, in plain torch on w's device."""
+    N, K = w.shape
+    if N < FP8_BLOCK or N % FP8_BLOCK or K < FP8_BLOCK or K % FP8_BLOCK:
+        raise ValueError(
+            f"N and K must be positive multiples of 128 (N={N}, K={K})")
+    nb, kb = N // FP8_BLOCK, K // FP8_BLOCK
+    wf = w.float().view(nb, FP8_BLOCK, kb, FP8_BLOCK)
+    q, scale = _quantize_groups_fp8(wf, wf.abs().amax(dim=(1, 3),
+                                                      keepdim=True))
+    return q.view(N, K), scale.view(nb, kb).contiguous()
+
+
+def fp8_block_linear(a_q, a_s, w_q, w_s):
+    """Emulated block-scaled e4m3 GEMM -> f32 [R, N]: a_q [R, K] with a_s
+    [K/128, R], w_q [N, K] with w_s [N/128, K/128]. For kb ascending
+
+        acc += (a_q[:, kb] @ w_q[:, kb].T in f32)
+               * (a_s[kb, :, None] * w_s[None, n // 128, kb])
+
+    where [:, kb] is the kb-th group of 128 K elements and the factor is one
+    f32 product. The kernel (csrc/gemm_tn_fp8_block_pipe.hip) may contract
+    the multiply-add into an fma."""
+    R, K = a_q.shape
+    N = w_q.shape[0]
+    af, wf = a_q.float(), w_q.float()
+    acc = torch.zeros(R, N, dtype=torch.float32, device=a_q.device)
+    for kb in range(K // FP8_BLOCK):
+        ks = slice(kb * FP8_BLOCK, (kb + 1) * FP8_BLOCK)
+        p = af[:, ks] @ wf[:, ks].T
+        ws = w_s[:, kb].repeat_interleave(FP8_BLOCK)
+        acc += p * (a_s[kb].unsqueeze(1) * ws.unsqueeze(0))
+    return acc
+
+
+def linear_fp8_block128(x, w_q, w_s, residual=None):
+    """THE statement of the block-scaled dense projection
+    (csrc/gemm_tn_fp8_block_pipe.hip): x [T, K] -> out [T, N] in x's dtype,
+    for w_q [N, K] e4m3 + w_s [N/128, K/128] f32 (`weight`,
+    `weight_scale_inv`):
+
+        x_q, x_s = quantize_rows_fp8_block128(x)     (per row and K group)
+        y        = fp8_block_linear(x_q, x_s, w_q, w_s)   (f32)
+        y        = y + f32(residual)                  (when given)
+        out      = y rounded once to x's dtype"""
+    x_q, x_s = quantize_rows_fp8_block128(x)
+    y = fp8_block_linear(x_q, x_s, w_q, w_s)
+    if residual is not None:
+        y = y + residual.float()
+    return y.to(x.dtype)
+
+
+def gate_up_silu_fp8_block128(x, w_q, w_s):
+    """SwiGLU of the merged block-scaled gate_up projection: w_q [2I, K]
+    (gate rows first) + w_s [2I/128, K/128], I % 128 == 0; returns [T, I] in
+    x's dtype.
+
+        y   = fp8_block_linear(quantize_rows_fp8_block128(x), w_q, w_s)
+        out = silu(y[:, :I]) * y[:, I:] in f32, rounded once
+
+    As in `gate_up_silu_fp8`, the two products are not rounded before the
+    activation."""
+    x_q, x_s = quantize_rows_fp8_block128(x)
+    y = fp8_block_linear(x_q, x_s, w_q, w_s)
+    inter = w_q.shape[0] // 2
+    return (torch.nn.functional.silu(y[:, :inter]) * y[:, inter:]).to(x.dtype)
+
+
 def grouped_gemm_fp8(out, a_q, a_scale, w_q, w_scale, row_tok, tile_off,
                      counts, max_tiles, gate_silu, bm: int = 64):
     """Reference for grouped_gemm_fp8 (csrc/grouped_gemm_fp8.hip) and the CPU

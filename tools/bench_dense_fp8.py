@@ -1,12 +1,17 @@
-"""Micro-benchmark of the dense W8A8 projections (csrc/gemm_tn_fp8_pipe.hip)
-against what the bf16 model runs for the same projection, all in ONE process.
+"""Micro-benchmark of the dense FP8 projections, per-channel W8A8
+(csrc/gemm_tn_fp8_pipe.hip) and block-scaled (csrc/gemm_tn_fp8_block_pipe.hip,
+dense_weight_dtype="fp8_block128"), against what the bf16 model runs for the
+same projection, all in ONE process.
 
 Per Qwen3-32B projection shape and token count M it times
   (a) the activation row quantiser (ops.quantize_rows_fp8),
   (b) the FP8 GEMM on pre-quantised operands,
   (c) the bf16 path: the library GEMM, or ops.gate_up_silu for gate_up (the
       library pair or the fused bf16 kernel, as GATE_UP_FUSED_RULE routes M),
-and reports TF/s of (b) and (c) and the ratio (a + b) / c.
+  (d) the 128-wide group quantiser (ops.quantize_rows_fp8_block128),
+  (e) the block-scaled GEMM on pre-quantised operands,
+and reports TF/s of (b), (c) and (e) and the ratios (a + b) / c, (d + e) / c
+and (d + e) / (a + b).
 
 Method of tools/bench_gate_up.py: variants alternate round by round; each
 round times a window of back-to-back calls per variant; median (min-max)
@@ -78,20 +83,29 @@ def main():
           f"{NSETS} device={torch.cuda.get_device_name(0)}", flush=True)
     rows = ["shape,M,N,K,quant_us,fp8_gemm_us,bf16_us,quant_min_us,"
             "quant_max_us,fp8_min_us,fp8_max_us,bf16_min_us,bf16_max_us,"
-            "fp8_gemm_tflops,bf16_tflops,ratio_quant_plus_gemm_over_bf16"]
+            "fp8_gemm_tflops,bf16_tflops,ratio_quant_plus_gemm_over_bf16,"
+            "block_quant_us,block_gemm_us,block_quant_min_us,"
+            "block_quant_max_us,block_gemm_min_us,block_gemm_max_us,"
+            "block_gemm_tflops,ratio_block_over_bf16,"
+            "ratio_block_over_per_channel"]
     for label, N, K in SHAPES:
         g = torch.Generator(device="cuda")
         g.manual_seed(N + K)
         ws = [(torch.randn(N, K, device="cuda", generator=g) / K ** 0.5)
               .bfloat16() for _ in range(NSETS)]
         wq = [quantize(w) for w in ws]
+        wb = [torch_ref.quantize_weight_fp8_block128(w) for w in ws]
         for M in ms:
             xs = [torch.randn(M, K, device="cuda", generator=g).bfloat16()
                   for _ in range(NSETS)]
             xq = [quantize(x) for x in xs]
+            xb = [ops.quantize_rows_fp8_block128(x) for x in xs]
             if label == "gate_up":
                 def fp8(i):
                     _C.gemm_fp8_gate_up_silu(*xq[i], *wq[i], 1)
+
+                def blk(i):
+                    _C.gemm_fp8_block_gate_up_silu(*xb[i], *wb[i], 1)
 
                 def bf16(i):
                     ops.gate_up_silu(xs[i], ws[i])
@@ -99,13 +113,20 @@ def main():
                 def fp8(i):
                     _C.gemm_fp8_pipelined(*xq[i], *wq[i], None, 1)
 
+                def blk(i):
+                    _C.gemm_fp8_block_pipelined(*xb[i], *wb[i], None, 1)
+
                 def bf16(i):
                     F.linear(xs[i], ws[i])
 
             def quant(i):
                 ops.quantize_rows_fp8(xs[i], *xq[i])
 
-            vs = [("quant", quant), ("fp8", fp8), ("bf16", bf16)]
+            def bquant(i):
+                ops.quantize_rows_fp8_block128(xs[i])
+
+            vs = [("quant", quant), ("fp8", fp8), ("bf16", bf16),
+                  ("bquant", bquant), ("blk", blk)]
             times = {name: [] for name, _ in vs}
             for r in range(args.rounds + 1):  # round 0 warms up
                 for name, fn in vs:
@@ -115,20 +136,29 @@ def main():
             med = {n: statistics.median(t) for n, t in times.items()}
             flops = 2.0 * M * N * K
             ratio = (med["quant"] + med["fp8"]) / med["bf16"]
+            bratio = (med["bquant"] + med["blk"]) / med["bf16"]
+            bover = (med["bquant"] + med["blk"]) / (med["quant"] + med["fp8"])
             rows.append(
                 f"{label},{M},{N},{K},{med['quant']:.1f},{med['fp8']:.1f},"
                 f"{med['bf16']:.1f},"
                 + ",".join(f"{f(times[n]):.1f}" for n in ("quant", "fp8", "bf16")
                            for f in (min, max))
                 + f",{flops / med['fp8'] / 1e6:.1f},"
-                f"{flops / med['bf16'] / 1e6:.1f},{ratio:.3f}")
+                f"{flops / med['bf16'] / 1e6:.1f},{ratio:.3f},"
+                f"{med['bquant']:.1f},{med['blk']:.1f},"
+                + ",".join(f"{f(times[n]):.1f}" for n in ("bquant", "blk")
+                           for f in (min, max))
+                + f",{flops / med['blk'] / 1e6:.1f},{bratio:.3f},{bover:.3f}")
             print(f"{label:8s} M={M:6d} N={N} K={K}: quant {med['quant']:8.1f}"
                   f" us  fp8 {med['fp8']:9.1f} us ({flops / med['fp8'] / 1e6:7.1f}"
                   f" TF/s)  bf16 {med['bf16']:9.1f} us "
                   f"({flops / med['bf16'] / 1e6:7.1f} TF/s)  (a+b)/c "
-                  f"{ratio:.3f}", flush=True)
-            del xs, xq
-        del ws, wq
+                  f"{ratio:.3f}  | block: quant {med['bquant']:8.1f} us  gemm "
+                  f"{med['blk']:9.1f} us ({flops / med['blk'] / 1e6:7.1f} TF/s)"
+                  f"  (d+e)/c {bratio:.3f}  (d+e)/(a+b) {bover:.3f}",
+                  flush=True)
+            del xs, xq, xb
+        del ws, wq, wb
         torch.cuda.empty_cache()
 
     outd = os.environ.get("BENCH_OUT", "bench_outputs")

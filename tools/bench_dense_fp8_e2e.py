@@ -1,7 +1,8 @@
 """End-to-end effect of dense_weight_dtype on decode: bench.py has no switch
-for it, so this builds the engine directly with the option off and on, at
+for it, so this builds the engine directly with each of its values ("bf16",
+"fp8_e4m3", "fp8_block128"), at
 bench.py's default operating point (Qwen3-32B, 2048 rows, prompt 128, 128 new
-tokens), and reports ms per decode step and resident KV blocks for both.
+tokens), and reports ms per decode step and resident KV blocks for each.
 
 Per setting: a fresh engine kept saturated the way bench.py keeps it (rows
 of `--prompt-len` random tokens, finished rows — random weights do sample
@@ -40,6 +41,9 @@ from sutro_amd.engine.engine import LLMEngine  # noqa: E402
 from sutro_amd.engine.request import SamplingParams  # noqa: E402
 from sutro_amd.models.registry import (get_model_spec,  # noqa: E402
                                        tiny_spec_for_tests)
+
+
+SETTINGS = ("bf16", "fp8_e4m3", "fp8_block128")
 
 
 def run(args, dense, gpu):
@@ -132,7 +136,7 @@ def main():
     ap.add_argument("--tokens-per-step", type=int, default=32768)
     ap.add_argument("--steps", type=int, default=32)
     ap.add_argument("--warmup", type=int, default=8)
-    ap.add_argument("--only", choices=["bf16", "fp8_e4m3"], default=None,
+    ap.add_argument("--only", choices=list(SETTINGS), default=None,
                     help="run one setting in this process and print its "
                          "result as a JSON line (what the tool starts, one "
                          "fresh process per setting, so that the memory "
@@ -151,7 +155,7 @@ def main():
         print("RESULT " + json.dumps(run(args, args.only, gpu)), flush=True)
         return
     lines = [",".join(cols)]
-    for dense in ("bf16", "fp8_e4m3"):
+    for dense in SETTINGS:
         r = None
         with subprocess.Popen([sys.executable, __file__, "--only", dense]
                               + sys.argv[1:], stdout=subprocess.PIPE,
