@@ -95,6 +95,15 @@ int sutro_gemm_tn_fp8_block_pipe_launch(void*, const void*, const float*,
 int sutro_gemm_tn_fp8_pipe_launch(void*, const void*, const float*,
                                   const void*, const float*, const void*, int,
                                   int, long, int, int, hipStream_t);
+void sutro_grouped_gemm_fp8_block(void*, const void*, const float*, long,
+                                  const void*, const float*, const int*,
+                                  const int*, int, int, int, long, int,
+                                  hipStream_t);
+void sutro_grouped_gemm_fp8_block_gate_q(void*, float*, long, const void*,
+                                         const float*, long, const void*,
+                                         const float*, const int*, const int*,
+                                         const int*, int, int, int, long, int,
+                                         hipStream_t);
 }
 
 void rmsnorm(torch::Tensor out, torch::Tensor x, torch::Tensor w, double eps) {
@@ -579,6 +588,141 @@ torch::Tensor gemm_fp8_block_gate_up_silu(torch::Tensor a_q,
   return out;
 }
 
+// quant_rows_fp8_block128 into caller-owned tensors (a preallocated
+// workspace: nothing is allocated under hipGraph capture): out_q [>= R, K]
+// e4m3, out_s [K/128, >= R] f32 whose rows may be strided.
+void quant_rows_fp8_block128_out(torch::Tensor x, torch::Tensor out_q,
+                                 torch::Tensor out_s) {
+  CHECK_CUDA(x); CHECK_CONTIG(x); CHECK_BF16(x);
+  CHECK_CUDA(out_q); CHECK_CONTIG(out_q); CHECK_CUDA(out_s);
+  TORCH_CHECK(x.dim() == 2 && out_q.dim() == 2 && out_s.dim() == 2,
+              "x, out_q, out_s must be 2-d");
+  TORCH_CHECK(is_fp8(out_q), "out_q must be float8_e4m3fn");
+  TORCH_CHECK(out_s.scalar_type() == at::kFloat, "out_s must be f32");
+  const long R = x.size(0), K = x.size(1);
+  TORCH_CHECK(K >= 128 && K % 128 == 0,
+              "K must be a positive multiple of 128 (K=", K, ")");
+  TORCH_CHECK(out_q.size(1) == K && out_q.size(0) >= R,
+              "out_q must be [>= R, K]");
+  TORCH_CHECK(out_s.size(0) == K / 128 && out_s.size(1) >= R,
+              "out_s must be [K/128, >= R]");
+  // (a dimension of size 1 carries no meaningful stride)
+  TORCH_CHECK((out_s.size(1) == 1 || out_s.stride(1) == 1)
+              && (K == 128 || out_s.stride(0) >= R),
+              "out_s rows must be dense");
+  sutro_quant_rows_fp8_block128(out_q.data_ptr(), out_s.data_ptr<float>(),
+                                x.data_ptr(), R, K,
+                                K == 128 ? out_s.size(1) : out_s.stride(0),
+                                cur_stream());
+}
+
+// shared operand checks of the two block-scaled grouped GEMM bindings: a_q
+// [rows, K] e4m3 + a_s [K/128, rows] f32 (rows may be strided), w_q [E, N, K]
+// e4m3 + w_s [E, N/128, K/128] f32, the segment tables. Returns the row
+// stride of a_s.
+static long check_grouped_fp8_block_args(
+    const torch::Tensor& a_q, const torch::Tensor& a_s,
+    const torch::Tensor& w_q, const torch::Tensor& w_s,
+    const torch::Tensor& tile_off, const torch::Tensor& counts, long n_cols,
+    long max_tiles, long bm) {
+  TORCH_CHECK(bm == 64 || bm == 128, "bm must be 64 or 128");
+  CHECK_CUDA(a_q); CHECK_CONTIG(a_q); CHECK_CUDA(w_q); CHECK_CONTIG(w_q);
+  TORCH_CHECK(is_fp8(a_q) && is_fp8(w_q), "a_q, w_q must be float8_e4m3fn");
+  CHECK_CUDA(a_s); CHECK_CUDA(w_s); CHECK_CONTIG(w_s);
+  TORCH_CHECK(a_s.scalar_type() == at::kFloat
+              && w_s.scalar_type() == at::kFloat, "scales must be f32");
+  TORCH_CHECK(w_q.dim() == 3 && w_s.dim() == 3 && a_q.dim() == 2
+              && a_s.dim() == 2, "ranks");
+  const long E = w_q.size(0), N = w_q.size(1), K = w_q.size(2);
+  TORCH_CHECK(K >= 128 && K % 128 == 0 && n_cols >= 128 && n_cols % 128 == 0,
+              "needs K and n_cols positive multiples of 128 (K=", K,
+              ", n_cols=", n_cols, ")");
+  TORCH_CHECK(N < (1L << 31) && K < (1L << 31), "N/K too large");
+  TORCH_CHECK(a_q.size(1) == K, "A K mismatch");
+  TORCH_CHECK(w_s.size(0) == E && w_s.size(1) == N / 128
+              && w_s.size(2) == K / 128, "w_s must be [E, N/128, K/128]");
+  TORCH_CHECK(a_s.size(0) == K / 128 && a_s.size(1) >= a_q.size(0),
+              "a_s must be [K/128, >= rows of a_q]");
+  TORCH_CHECK((a_s.size(1) == 1 || a_s.stride(1) == 1)
+              && (K == 128 || a_s.stride(0) >= a_s.size(1)),
+              "a_s rows must be dense");
+  CHECK_CUDA(tile_off); CHECK_CUDA(counts);
+  TORCH_CHECK(tile_off.scalar_type() == at::kInt
+              && counts.scalar_type() == at::kInt, "tile_off/counts int32");
+  TORCH_CHECK(tile_off.numel() == E + 1 && counts.numel() == E, "seg sizes");
+  TORCH_CHECK(max_tiles >= 0 && max_tiles * bm < (1L << 31), "max_tiles");
+  return K == 128 ? a_s.size(1) : a_s.stride(0);
+}
+
+// plain stage of the block-scaled grouped GEMM (csrc/
+// grouped_gemm_fp8_block.hip): out [rows, N] bf16 over padded segments.
+void grouped_gemm_fp8_block128(torch::Tensor out, torch::Tensor a_q,
+                               torch::Tensor a_s, torch::Tensor w_q,
+                               torch::Tensor w_s, torch::Tensor tile_off,
+                               torch::Tensor counts, long max_tiles,
+                               long bm) {
+  const long lda_s = check_grouped_fp8_block_args(
+      a_q, a_s, w_q, w_s, tile_off, counts, w_q.size(1), max_tiles, bm);
+  const long E = w_q.size(0), N = w_q.size(1), K = w_q.size(2);
+  CHECK_CUDA(out); CHECK_CONTIG(out); CHECK_BF16(out);
+  TORCH_CHECK(out.dim() == 2 && out.size(1) == N, "out width mismatch");
+  TORCH_CHECK(out.size(0) >= max_tiles * bm,
+              "out holds fewer rows than max_tiles * bm");
+  TORCH_CHECK(a_q.size(0) >= max_tiles * bm,
+              "a_q holds fewer rows than max_tiles * bm");
+  // a lane reads the scales of its 4 accumulator rows as 16 bytes
+  TORCH_CHECK((uintptr_t)a_s.data_ptr() % 16 == 0 && lda_s % 4 == 0,
+              "a_s must be 16-byte aligned with a row stride % 4 == 0");
+  sutro_grouped_gemm_fp8_block(
+      out.data_ptr(), a_q.data_ptr(), a_s.data_ptr<float>(), lda_s,
+      w_q.data_ptr(), w_s.data_ptr<float>(), tile_off.data_ptr<int>(),
+      counts.data_ptr<int>(), (int)E, (int)max_tiles, (int)N, K, (int)bm,
+      cur_stream());
+}
+
+// stage 1 of the block-scaled grouped GEMM: gate/up through row_tok, SwiGLU,
+// and the 128-group quantiser in the epilogue: act_q [rows, I] e4m3 + act_s
+// [I/128, rows] f32 (rows may be strided), the stage-2 input.
+void grouped_gemm_fp8_block128_gate_q(torch::Tensor act_q,
+                                      torch::Tensor act_s, torch::Tensor a_q,
+                                      torch::Tensor a_s, torch::Tensor w_q,
+                                      torch::Tensor w_s,
+                                      torch::Tensor row_tok,
+                                      torch::Tensor tile_off,
+                                      torch::Tensor counts, long max_tiles,
+                                      long bm) {
+  TORCH_CHECK(w_q.dim() == 3 && w_q.size(1) % 2 == 0, "w_q must be [E, 2I, K]");
+  const long I = w_q.size(1) / 2;
+  const long lda_s = check_grouped_fp8_block_args(
+      a_q, a_s, w_q, w_s, tile_off, counts, I, max_tiles, bm);
+  const long E = w_q.size(0), K = w_q.size(2);
+  CHECK_CUDA(act_q); CHECK_CONTIG(act_q); CHECK_CUDA(act_s);
+  TORCH_CHECK(is_fp8(act_q) && act_s.scalar_type() == at::kFloat,
+              "act_q must be float8_e4m3fn, act_s f32");
+  TORCH_CHECK(act_q.dim() == 2 && act_q.size(1) == I
+              && act_q.size(0) >= max_tiles * bm,
+              "act_q must be [>= max_tiles * bm, I]");
+  TORCH_CHECK((uintptr_t)act_q.data_ptr() % 16 == 0,
+              "act_q must be 16-byte aligned");
+  TORCH_CHECK(act_s.dim() == 2 && act_s.size(0) == I / 128
+              && act_s.size(1) >= max_tiles * bm,
+              "act_s must be [I/128, >= max_tiles * bm]");
+  TORCH_CHECK((act_s.size(1) == 1 || act_s.stride(1) == 1)
+              && (I == 128 || act_s.stride(0) >= act_s.size(1)),
+              "act_s rows must be dense");
+  CHECK_CUDA(row_tok);
+  TORCH_CHECK(row_tok.scalar_type() == at::kInt
+              && row_tok.numel() >= max_tiles * bm,
+              "row_tok must be int32 [>= max_tiles * bm]");
+  sutro_grouped_gemm_fp8_block_gate_q(
+      act_q.data_ptr(), act_s.data_ptr<float>(),
+      I == 128 ? act_s.size(1) : act_s.stride(0), a_q.data_ptr(),
+      a_s.data_ptr<float>(), lda_s, w_q.data_ptr(), w_s.data_ptr<float>(),
+      row_tok.data_ptr<int>(), tile_off.data_ptr<int>(),
+      counts.data_ptr<int>(), (int)E, (int)max_tiles, (int)I, K, (int)bm,
+      cur_stream());
+}
+
 torch::Tensor mfma32_probe(torch::Tensor a, torch::Tensor b) {
   CHECK_CUDA(a); CHECK_BF16(a);
   auto c = torch::zeros({32, 32}, a.options().dtype(at::kFloat));
@@ -988,4 +1132,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "SwiGLU fused into the block-scaled e4m3 gate_up GEMM",
         py::arg("a_q"), py::arg("a_s"), py::arg("w_q"), py::arg("w_s"),
         py::arg("xcd_swz") = 1);
+  m.def("quant_rows_fp8_block128_out", &quant_rows_fp8_block128_out,
+        "quant_rows_fp8_block128 into caller-owned codes and scales",
+        py::arg("x"), py::arg("out_q"), py::arg("out_s"));
+  m.def("grouped_gemm_fp8_block128", &grouped_gemm_fp8_block128,
+        "dropless MoE grouped GEMM, e4m3 with 128x128 weight scales (plain)");
+  m.def("grouped_gemm_fp8_block128_gate_q", &grouped_gemm_fp8_block128_gate_q,
+        "block-scaled grouped gate/up GEMM, SwiGLU, quantised stage-2 input");
 }

@@ -188,9 +188,12 @@ def models():
 @click.option("--port", default=8000, type=int)
 @click.option("--device", default="auto")
 @click.option("--moe-weight-dtype", default="bf16",
-              type=click.Choice(["bf16", "fp8_e4m3", "mxfp4"]),
+              type=click.Choice(["bf16", "fp8_e4m3", "mxfp4",
+                                 "fp8_block128"]),
               help="storage of MoE expert weights (fp8_e4m3 halves them, "
-                   "mxfp4 stores 4.25 bits per weight)")
+                   "mxfp4 stores 4.25 bits per weight, fp8_block128 is "
+                   "fp8 with the 128x128 block scales of the published FP8 "
+                   "checkpoints)")
 @click.option("--dense-weight-dtype", default="bf16",
               type=click.Choice(["bf16", "fp8_e4m3", "fp8_block128"]),
               help="storage of the dense projections (qkv, o, gate_up, down; "

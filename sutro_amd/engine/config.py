@@ -65,6 +65,12 @@ class EngineConfig:
     # hands one engine_kwargs to every model).
     # "mxfp4": OCP MX e2m1 codes with one e8m0 scale per 32 K-elements (4.25
     # bits per weight), dequantised inside the block-scaled MFMA (W4A8).
+    # "fp8_block128": OCP e4m3 with one f32 scale per 128x128 weight block
+    # per expert (the experts of the published block-FP8 checkpoints, which
+    # load without a bf16 stage) and activations quantised per token and
+    # 128-wide K group, on csrc/grouped_gemm_fp8_block.hip; stage 1 writes
+    # the quantised stage-2 input itself. Needs the hidden size and the local
+    # expert intermediate size to be multiples of 128.
     moe_weight_dtype: str = "bf16"
     # "bf16" (default) or "fp8_e4m3": store the dense projections (qkv / o of
     # every attention block, gate_up / down of every dense MLP) as OCP e4m3
@@ -121,10 +127,11 @@ class EngineConfig:
                 f"{self.spec.sliding_window_pattern})")
         if self.spec.embedding:
             self.enable_prefix_caching = False
-        if self.moe_weight_dtype not in ("bf16", "fp8_e4m3", "mxfp4"):
+        if self.moe_weight_dtype not in ("bf16", "fp8_e4m3", "mxfp4",
+                                         "fp8_block128"):
             raise ValueError(
-                f"moe_weight_dtype must be 'bf16', 'fp8_e4m3' or 'mxfp4', "
-                f"got {self.moe_weight_dtype!r}")
+                f"moe_weight_dtype must be 'bf16', 'fp8_e4m3', 'mxfp4' or "
+                f"'fp8_block128', got {self.moe_weight_dtype!r}")
         if self.dense_weight_dtype not in ("bf16", "fp8_e4m3",
                                            "fp8_block128"):
             raise ValueError(

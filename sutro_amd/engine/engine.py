@@ -109,6 +109,10 @@ class LLMEngine:
                     if cfg.moe_weight_dtype == "mxfp4":
                         # a no-op on experts loaded pre-quantised
                         mod.quantize_experts_mxfp4()
+                    elif cfg.moe_weight_dtype == "fp8_block128":
+                        # likewise; a shard that is not whole 128x128 blocks
+                        # is a ValueError, never a fallback
+                        mod.quantize_experts_fp8_block128()
                     else:
                         mod.quantize_experts_fp8()
             if cfg.device.startswith("cuda"):

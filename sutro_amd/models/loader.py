@@ -39,6 +39,20 @@ model under its own merged names, so the file reloads the same way. The
 model is still built in bf16 before such a load, so peak memory at load is
 the bf16 model's.
 
+Block-FP8 experts (`moe_weight_dtype="fp8_block128"`): the experts of the same
+published checkpoints, `<...>.mlp.experts.<E>.<gate|up|down>_proj.weight` of
+dtype float8_e4m3fn with `.weight_scale_inv` f32 [N/128, K/128]. gate and up
+are concatenated along N (codes) and dim 0 (scales), the experts are stacked
+to [E, N, K] / [E, N/128, K/128], the stack is cut for TP (gate_up along N per
+section, down along K, both on the block grid: a cut off the grid is an error)
+or EP (dim 0), and `Qwen3MoE.load_expert_fp8_block128` installs it bit for
+bit, without a bf16 stage. `save_weights` writes block-quantised experts under
+the model's own stacked names, `<...>.mlp.gate_up` (e4m3) +
+`.gate_up_scale_inv` and `.down` + `.down_scale_inv`, which load the same way.
+An incomplete pair, a wrong scale shape or dtype is a ValueError. With any
+other `moe_weight_dtype` an e4m3 expert tensor is an error; bf16 experts load
+as always and are quantised at engine start-up.
+
 Attention sinks (`EngineConfig.local_attention` with a spec that has them):
 the parameter is `layers.N.self_attn.sinks`, f32 [num_heads], the name gpt-oss
 checkpoints use (`model.layers.N.self_attn.sinks`); it is sliced with the q
@@ -99,6 +113,12 @@ def _shard_slice(p: torch.nn.Parameter, full: torch.Tensor) -> torch.Tensor:
 
 _FP8_SCALE_SUFFIX = ".weight_scale_inv"
 
+# block-FP8 experts: the published per-expert pairs and the stacked pair
+# `save_weights` writes
+_EXPERT_FP8_RE = re.compile(
+    r"^(.*\.mlp)\.experts\.(\d+)\.(gate|up|down)_proj\.weight(_scale_inv)?$")
+_EXPERT_STACK_FP8_RE = re.compile(r"^(.*\.mlp)\.(gate_up|down)(_scale_inv)?$")
+
 
 def _check_quantization_config(path: str) -> None:
     """A config.json with a quantization_config must describe the one
@@ -122,11 +142,17 @@ def _check_quantization_config(path: str) -> None:
 def _shard_slice_fp8_block(p: torch.nn.Parameter, name: str,
                            codes: torch.Tensor, scales: torch.Tensor):
     """`_shard_slice` for a block-quantised pair: codes [N, K] and scales
-    [N/128, K/128] are cut together, so every cut must fall on a block."""
+    [N/128, K/128] are cut together, so every cut must fall on a block.
+    Stacked experts ([E, N, K] / [E, N/128, K/128]) are cut the same way;
+    along dim 0 (expert parallelism) whole experts go, off no grid."""
     tp_size = getattr(p, "_tp_size", 1)
     if tp_size <= 1 or tuple(codes.shape) == tuple(p.shape):
         return codes, scales
     dim, rank = p._tp_dim, p._tp_rank
+    if codes.dim() == 3 and dim == 0:
+        per = codes.shape[0] // tp_size
+        return (codes.narrow(0, rank * per, per),
+                scales.narrow(0, rank * per, per))
     sections = p._tp_sections or [(0, codes.shape[dim])]
     c_parts, s_parts = [], []
     for start, length in sections:
@@ -193,9 +219,29 @@ def load_weights(model: torch.nn.Module, path: str, strict: bool = True,
         return None
 
     pending_experts: Dict[str, Dict[Tuple[int, str], torch.Tensor]] = {}
+    # block-FP8 experts: mlp prefix -> (expert, part) -> {"weight", "scale"};
+    # the stacked form: (mlp prefix, gate_up|down) -> {"weight", "scale"}
+    pending_experts_fp8: Dict[str, Dict[Tuple[int, str],
+                                        Dict[str, torch.Tensor]]] = {}
+    pending_stack_fp8: Dict[Tuple[str, str], Dict[str, torch.Tensor]] = {}
+    f8 = torch.float8_e4m3fn
     unexpected: List[str] = []
     for raw_name, tensor in _iter_safetensors(path):
         name = _canon(raw_name)
+        if moe_weight_dtype == "fp8_block128":
+            em = _EXPERT_FP8_RE.match(name)
+            if (em and f"{em.group(1)}.gate_up" in params
+                    and (em.group(4) or tensor.dtype == f8)):
+                pending_experts_fp8.setdefault(em.group(1), {}).setdefault(
+                    (int(em.group(2)), em.group(3)), {})[
+                        "scale" if em.group(4) else "weight"] = tensor
+                continue
+            sm = _EXPERT_STACK_FP8_RE.match(name)
+            if (sm and f"{sm.group(1)}.gate_up" in params
+                    and (sm.group(3) or tensor.dtype == f8)):
+                pending_stack_fp8.setdefault((sm.group(1), sm.group(2)), {})[
+                    "scale" if sm.group(3) else "weight"] = tensor
+                continue
         is_scale = name.endswith(_FP8_SCALE_SUFFIX)
         if is_scale or tensor.dtype == torch.float8_e4m3fn:
             wname = name[: -len("_scale_inv")] if is_scale else name
@@ -309,6 +355,53 @@ def load_weights(model: torch.nn.Module, path: str, strict: bool = True,
                         f"incomplete expert tensors for {prefix} expert {e}")
             assign(pname, torch.stack(full_e))
 
+    def fp8_pair(what: str, pair: Dict[str, torch.Tensor], lead: int):
+        """a complete, well-formed (codes, scale_inv) pair or a ValueError;
+        `lead` = leading stack dims (0: one expert's projection, 1: stacked)"""
+        if sorted(pair) != ["scale", "weight"]:
+            raise ValueError(
+                f"incomplete FP8 pair for {what}: needs both the e4m3 tensor "
+                f"and its scale_inv, has {sorted(pair)}")
+        wq, sc = pair["weight"], pair["scale"]
+        want = tuple(wq.shape[:lead]) + tuple(d // 128 for d in wq.shape[lead:])
+        if (wq.dtype != f8 or wq.dim() != lead + 2
+                or any(d % 128 for d in wq.shape[lead:])
+                or sc.dtype != torch.float32 or tuple(sc.shape) != want):
+            raise ValueError(
+                f"bad FP8 pair for {what}: {wq.dtype} {tuple(wq.shape)} needs "
+                f"float8_e4m3fn with N % 128 == 0, K % 128 == 0 and a float32 "
+                f"scale_inv {want}, got {sc.dtype} {tuple(sc.shape)}")
+        return wq, sc
+
+    for prefix, parts in pending_experts_fp8.items():
+        n_exp = max(e for e, _ in parts) + 1
+        for which, need in (("gate_up", ("gate", "up")), ("down", ("down",))):
+            if not any(k in need for _, k in parts):
+                continue  # this projection came unquantised
+            pairs = []
+            for e in range(n_exp):
+                for k in need:
+                    if (e, k) not in parts:
+                        raise ValueError(f"incomplete FP8 expert tensors for "
+                                         f"{prefix} expert {e} ({k}_proj)")
+                pairs.append([fp8_pair(f"{prefix}.experts.{e}.{k}_proj",
+                                       parts[(e, k)], 0) for k in need])
+            pending_stack_fp8[(prefix, which)] = {
+                "weight": torch.stack([torch.cat([c for c, _ in pr], dim=0)
+                                       for pr in pairs]),
+                "scale": torch.stack([torch.cat([s for _, s in pr], dim=0)
+                                      for pr in pairs])}
+
+    for (prefix, which), pair in pending_stack_fp8.items():
+        pname = f"{prefix}.{which}"
+        if pname in loaded:
+            raise ValueError(f"{pname} comes both quantised and unquantised")
+        codes, scales = fp8_pair(pname, pair, 1)
+        codes, scales = _shard_slice_fp8_block(params[pname], pname, codes,
+                                               scales)
+        modules[prefix].load_expert_fp8_block128(which, codes, scales)
+        loaded.add(pname)
+
     for (prefix, which), pair in pending_mxfp4.items():
         if sorted(pair) != ["blocks", "scales"]:
             raise ValueError(f"incomplete MXFP4 pair for {prefix}.{which}: "
@@ -362,5 +455,10 @@ def save_weights(model: torch.nn.Module, path: str) -> str:
                     getattr(mod, which).detach().cpu().contiguous())
                 state[f"{prefix}.{which}_scales"] = (
                     getattr(mod, which + "_scales").detach().cpu().contiguous())
+        if getattr(mod, "experts_fp8_block128", False):
+            for which in ("gate_up", "down"):
+                for name in (which, which + "_scale_inv"):
+                    state[f"{prefix}.{name}"] = (
+                        getattr(mod, name).detach().cpu().contiguous())
     save_file(state, out)
     return out

@@ -345,7 +345,16 @@ class Qwen3MoE(nn.Module):
 
     @property
     def experts_fp8(self) -> bool:
-        return self.gate_up.dtype == torch.float8_e4m3fn
+        """per-output-channel e4m3 experts (`gate_up_scale`); block-scaled
+        experts store e4m3 too and are told apart by their scale buffer"""
+        return (self.gate_up.dtype == torch.float8_e4m3fn
+                and not self.experts_fp8_block128)
+
+    @property
+    def experts_fp8_block128(self) -> bool:
+        """e4m3 experts with one f32 scale per 128x128 block
+        (`gate_up_scale_inv`, `down_scale_inv`)"""
+        return "gate_up_scale_inv" in self._buffers
 
     @property
     def experts_mxfp4(self) -> bool:
@@ -360,7 +369,7 @@ class Qwen3MoE(nn.Module):
         on the LOCAL shard after TP/EP sharding and frees the bf16 tensor of
         each projection before the next one is quantised. Idempotent; refuses
         to run on FP8 experts (their bf16 source is gone)."""
-        if self.experts_fp8:
+        if self.experts_fp8 or self.experts_fp8_block128:
             raise RuntimeError("experts are already quantised to fp8_e4m3; "
                                "mxfp4 needs the unquantised weights")
         for name in ("gate_up", "down"):
@@ -378,7 +387,7 @@ class Qwen3MoE(nn.Module):
                           scales: torch.Tensor) -> None:
         """Install a pre-quantised projection (`gate_up` or `down`) of the
         local shard, bit for bit: the bf16 parameter is dropped unread."""
-        if self.experts_fp8:
+        if self.experts_fp8 or self.experts_fp8_block128:
             raise RuntimeError("experts are already quantised to fp8_e4m3")
         w = getattr(self, name)
         E, N = w.shape[:2]
@@ -417,9 +426,10 @@ class Qwen3MoE(nn.Module):
         quantised. Idempotent."""
         if self.experts_fp8:
             return
-        if self.experts_mxfp4:
-            raise RuntimeError("experts are already quantised to mxfp4; "
-                               "fp8_e4m3 needs the unquantised weights")
+        if self.experts_mxfp4 or self.experts_fp8_block128:
+            raise RuntimeError("experts are already quantised to mxfp4 or "
+                               "fp8_block128; fp8_e4m3 needs the unquantised "
+                               "weights")
         for name in ("gate_up", "down"):
             w = getattr(self, name).data.contiguous()
             E, N, K = w.shape
@@ -434,12 +444,96 @@ class Qwen3MoE(nn.Module):
             self.register_buffer(name, w_q)
             self.register_buffer(name + "_scale", scale)
 
+    def _check_fp8_block128_shapes(self) -> None:
+        """the block-scaled grouped GEMM takes whole 128x128 blocks of the
+        LOCAL shard only; there is no fallback"""
+        h = self.down.shape[1]
+        m_l = self.gate_up.shape[1] // 2
+        if not (ops.grouped_gemm_fp8_block128_qualifies(m_l, h)
+                and ops.grouped_gemm_fp8_block128_qualifies(h, m_l)):
+            raise ValueError(
+                f"moe_weight_dtype='fp8_block128' needs the hidden size and "
+                f"the local expert intermediate size to be multiples of 128; "
+                f"this shard has hidden {h}, intermediate {m_l}")
+
+    @torch.no_grad()
+    def quantize_experts_fp8_block128(self) -> None:
+        """Replace gate_up / down by OCP e4m3 codes [E, N, K] plus one f32
+        scale per 128x128 block, [E, N/128, K/128] (`gate_up_scale_inv`,
+        `down_scale_inv`) — per expert the format of
+        torch_ref.quantize_weight_fp8_block128, i.e. of the published
+        block-FP8 checkpoints. Quantises the LOCAL shard, after sharding, and
+        frees the bf16 tensor of each projection before the next one is
+        quantised. Idempotent (a projection that was loaded pre-quantised
+        stays as it is); refuses experts in another quantised mode."""
+        if self.experts_mxfp4 or self.experts_fp8:
+            raise RuntimeError("experts are already quantised to mxfp4 or "
+                               "fp8_e4m3; fp8_block128 needs the unquantised "
+                               "weights")
+        self._check_fp8_block128_shapes()
+        for name in ("gate_up", "down"):
+            if name + "_scale_inv" in self._buffers:
+                continue  # done before, or loaded pre-quantised
+            w = getattr(self, name).data.contiguous()
+            E, N, K = w.shape
+            codes = torch.empty(E, N, K, dtype=torch.float8_e4m3fn,
+                                device=w.device)
+            scale_inv = torch.empty(E, N // 128, K // 128,
+                                    dtype=torch.float32, device=w.device)
+            for e in range(E):
+                codes[e], scale_inv[e] = (
+                    torch_ref.quantize_weight_fp8_block128(w[e]))
+            del self._parameters[name]
+            del w
+            self.register_buffer(name, codes)
+            self.register_buffer(name + "_scale_inv", scale_inv)
+
+    @torch.no_grad()
+    def load_expert_fp8_block128(self, name: str, codes: torch.Tensor,
+                                 scale_inv: torch.Tensor) -> None:
+        """Install a pre-quantised projection (`gate_up` or `down`) of the
+        local shard, bit for bit: the bf16 parameter is dropped unread."""
+        if self.experts_mxfp4 or self.experts_fp8:
+            raise RuntimeError("experts are already quantised to mxfp4 or "
+                               "fp8_e4m3")
+        self._check_fp8_block128_shapes()
+        w = getattr(self, name)
+        E, N, K = w.shape
+        if (codes.dtype != torch.float8_e4m3fn
+                or scale_inv.dtype != torch.float32
+                or tuple(codes.shape) != (E, N, K)
+                or tuple(scale_inv.shape) != (E, N // 128, K // 128)):
+            raise ValueError(
+                f"block-FP8 pair for {name} must be float8_e4m3fn "
+                f"{(E, N, K)} / float32 {(E, N // 128, K // 128)} (the local "
+                f"shard), got {codes.dtype} {tuple(codes.shape)} / "
+                f"{scale_inv.dtype} {tuple(scale_inv.shape)}")
+        dev = w.device
+        self._parameters.pop(name, None)
+        self._buffers.pop(name, None)
+        self._buffers.pop(name + "_scale_inv", None)
+        del w
+        self.register_buffer(name, codes.to(dev).contiguous())
+        self.register_buffer(name + "_scale_inv",
+                             scale_inv.to(dev).contiguous())
+
     def _expert_mlp(self, seg: torch.Tensor, e: int) -> torch.Tensor:
         """rows `seg` through local expert e (segment-loop paths). In FP8
         mode this is the kernel's arithmetic emulated: quantised rows, fp32
         sums, scales after the sum, SwiGLU in fp32, the activation rounded to
         the working dtype and quantised again. MXFP4 mode is the same with
-        exactly dequantised weights and no weight-side epilogue scale."""
+        exactly dequantised weights and no weight-side epilogue scale.
+        Block-FP8 mode is the statement of csrc/grouped_gemm_fp8_block.hip:
+        torch_ref.fp8_block_linear on 128-group-quantised rows, twice."""
+        if self.experts_fp8_block128:
+            m = self.gate_up.shape[1] // 2
+            x_q, x_s = ops.quantize_rows_fp8_block128(seg)
+            y = torch_ref.fp8_block_linear(x_q, x_s, self.gate_up[e],
+                                           self.gate_up_scale_inv[e])
+            act = (F.silu(y[:, :m]) * y[:, m:]).to(seg.dtype)
+            a_q, a_s = ops.quantize_rows_fp8_block128(act)
+            return torch_ref.fp8_block_linear(
+                a_q, a_s, self.down[e], self.down_scale_inv[e]).to(seg.dtype)
         mx = self.experts_mxfp4
         if not (self.experts_fp8 or mx):
             act = ops.silu_mul(seg @ self.gate_up[e].T)
@@ -472,7 +566,8 @@ class Qwen3MoE(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if x.is_cuda:
             if (self._PREFILL_BLASLT_MIN
-                    and not (self.experts_fp8 or self.experts_mxfp4)
+                    and not (self.experts_fp8 or self.experts_mxfp4
+                             or self.experts_fp8_block128)
                     and x.shape[0] >= self._PREFILL_BLASLT_MIN
                     and not torch.cuda.is_current_stream_capturing()):
                 # big eager waves: library GEMMs on true segment sizes
@@ -609,15 +704,20 @@ class Qwen3MoE(nn.Module):
         # activations keep the working dtype whatever the experts are stored in
         dtype = self.router.weight.dtype
         key = (str(dev), dtype, h, m_l, self.experts_per_rank)
+        blk = self.experts_fp8_block128
         if fp8:
             key += (self.gate_up.dtype,)
+        elif blk:
+            key += ("fp8_block128",)
         ws = _MOE_WS.get(key)
         if ws is None or ws["rows"] < rows_max or ws["max_T"] < T:
             rows_max = max(rows_max, ws["rows"] if ws else 0)
             T = max(T, ws["max_T"] if ws else 0)
             ws = {
                 "rows": rows_max,
-                "act": torch.empty(rows_max, m_l, dtype=dtype, device=dev),
+                # (block-FP8 stage 1 writes the quantised act_q directly)
+                "act": torch.empty(0 if blk else rows_max, m_l, dtype=dtype,
+                                   device=dev),
                 "out_sorted": torch.empty(rows_max, h, dtype=dtype,
                                           device=dev),
                 "row_tok": torch.empty(rows_max, dtype=torch.int32,
@@ -635,6 +735,20 @@ class Qwen3MoE(nn.Module):
                                           device=dev).view(f8)
                 ws["act_scale"] = torch.ones(rows_max, dtype=torch.float32,
                                              device=dev)
+            if blk:
+                # codes of both stage inputs and their K-block-major scales;
+                # the row stride of act_s is a multiple of 4 (stage 2 reads
+                # a lane's four rows as 16 bytes)
+                f8 = torch.float8_e4m3fn
+                rows_al = (rows_max + 3) // 4 * 4
+                ws["x_q"] = torch.zeros(T, h, dtype=torch.uint8,
+                                        device=dev).view(f8)
+                ws["x_s"] = torch.ones(h // 128, T, dtype=torch.float32,
+                                       device=dev)
+                ws["act_q"] = torch.zeros(rows_max, m_l, dtype=torch.uint8,
+                                          device=dev).view(f8)
+                ws["act_s"] = torch.ones(m_l // 128, rows_al,
+                                         dtype=torch.float32, device=dev)
             # zero once: rows past the padded total are never written, but
             # EP-invalid assignments gather them with weight 0 — torch.empty
             # garbage could be inf/NaN and 0*NaN = NaN
@@ -770,6 +884,18 @@ class Qwen3MoE(nn.Module):
             ops.grouped_gemm_mxfp4(out_sorted, a_q, a_s, self.down,
                                    self.down_scales, None, tile_off, counts,
                                    max_tiles, False, bm=BM)
+        elif self.experts_fp8_block128:
+            # quant(x) -> stage 1 (writes the quantised stage-2 input
+            # itself) -> stage 2, all into the workspace
+            x_q, x_s = ws["x_q"][:T], ws["x_s"][:, :T]
+            ops.quantize_rows_fp8_block128_out(x.contiguous(), x_q, x_s)
+            ops.grouped_gemm_fp8_block128_gate_q(
+                ws["act_q"], ws["act_s"], x_q, x_s, self.gate_up,
+                self.gate_up_scale_inv, row_tok, tile_off, counts, max_tiles,
+                bm=BM)
+            ops.grouped_gemm_fp8_block128(
+                out_sorted, ws["act_q"], ws["act_s"], self.down,
+                self.down_scale_inv, tile_off, counts, max_tiles, bm=BM)
         elif self.experts_fp8:
             # quant(x) -> stage 1 -> quant(act) -> stage 2, all into the
             # workspace; the second quant stops at the live padded total

@@ -669,6 +669,63 @@ def gate_up_silu_fp8_block128(x, w_q, w_s):
     return torch_ref.gate_up_silu_fp8_block128(x, w_q, w_s)
 
 
+def grouped_gemm_fp8_block128_qualifies(n: int, k: int) -> bool:
+    """Per-expert weight shapes [n, k] (n = the stage's output width: I for
+    gate_up, h for down) the block-scaled grouped GEMM takes: whole 128x128
+    scale blocks."""
+    return n >= 128 and n % 128 == 0 and k >= 128 and k % 128 == 0
+
+
+def quantize_rows_fp8_block128_out(x, out_q, out_s):
+    """`quantize_rows_fp8_block128` into caller-owned tensors (out_q
+    [>= R, K] e4m3, out_s [K/128, >= R] f32, rows may be strided): nothing is
+    allocated, so a layer can quantise into its workspace under hipGraph
+    capture."""
+    if _use_hip(x):
+        _require_hip().quant_rows_fp8_block128_out(x.contiguous(), out_q,
+                                                   out_s)
+        return out_q, out_s
+    q, s = torch_ref.quantize_rows_fp8_block128(x)
+    out_q.view(torch.uint8)[:x.shape[0]] = q.view(torch.uint8)
+    out_s[:, :x.shape[0]] = s
+    return out_q, out_s
+
+
+def grouped_gemm_fp8_block128(out, a_q, a_s, w_q, w_s, tile_off, counts,
+                              max_tiles, bm=64):
+    """Plain stage of the block-scaled grouped GEMM: a_q [rows, K] e4m3 + a_s
+    [K/128, rows] f32 in the padded-segment layout, w_q [E, N, K] e4m3 + w_s
+    [E, N/128, K/128] f32 (one scale per 128x128 block), bf16 out.
+    csrc/grouped_gemm_fp8_block.hip on GPU, torch_ref arithmetic on CPU."""
+    if _use_hip(a_q):
+        _require_hip().grouped_gemm_fp8_block128(out, a_q, a_s, w_q, w_s,
+                                                 tile_off, counts, max_tiles,
+                                                 bm)
+        return out
+    return torch_ref.grouped_gemm_fp8_block128(out, a_q, a_s, w_q, w_s,
+                                               tile_off, counts, max_tiles,
+                                               bm)
+
+
+def grouped_gemm_fp8_block128_gate_q(act_q, act_s, a_q, a_s, w_q, w_s,
+                                     row_tok, tile_off, counts, max_tiles,
+                                     bm=64):
+    """Stage 1 of the block-scaled grouped GEMM: tokens a_q [T, K] + a_s
+    [K/128, T] gathered through row_tok, w_q [E, 2I, K] (gate rows first) +
+    w_s [E, 2I/128, K/128], SwiGLU in f32, one rounding to bf16, and the
+    128-group quantiser in the epilogue: writes the stage-2 input act_q
+    [rows, I] e4m3 + act_s [I/128, rows] f32.
+    csrc/grouped_gemm_fp8_block.hip on GPU, torch_ref arithmetic on CPU."""
+    if _use_hip(a_q):
+        _require_hip().grouped_gemm_fp8_block128_gate_q(
+            act_q, act_s, a_q, a_s, w_q, w_s, row_tok, tile_off, counts,
+            max_tiles, bm)
+        return act_q, act_s
+    return torch_ref.grouped_gemm_fp8_block128_gate_q(
+        act_q, act_s, a_q, a_s, w_q, w_s, row_tok, tile_off, counts,
+        max_tiles, bm)
+
+
 def quantize_weight_mxfp4(w):
     """w [..., K] -> MXFP4 (e2m1 code pairs uint8 [..., Kp/2], e8m0 block
     scales uint8 [..., Kp/32]); the format and rule are stated in

@@ -420,6 +420,70 @@ def grouped_gemm_fp8(out, a_q, a_scale, w_q, w_scale, row_tok, tile_off,
     return out
 
 
+def _grouped_fp8_block128(a_q, a_s, w_q, w_s, row_tok, tile_off, counts, bm,
+                          gate_silu, store):
+    """Segment loop shared by the two block-scaled grouped GEMMs: per expert
+    segment, gather (codes and scales through the same index), block linear,
+    optionally SwiGLU in f32, round to bf16; `store(s0, c, y)` takes the live
+    rows [s0, s0 + c) of the padded layout."""
+    E, N, _ = w_q.shape
+    n_cols = N // 2 if gate_silu else N
+    for e in range(E):
+        c = int(counts[e])
+        if c == 0:
+            continue
+        s0 = int(tile_off[e]) * bm
+        if row_tok is not None:
+            idx = row_tok[s0:s0 + c].long().clamp(min=0)
+        else:
+            idx = torch.arange(s0, s0 + c, device=a_q.device)
+        # index the byte view: fp8 tensors have no gather kernels everywhere
+        rows = a_q.view(torch.uint8)[idx].view(torch.float8_e4m3fn)
+        y = fp8_block_linear(rows, a_s[:, idx], w_q[e], w_s[e])
+        if gate_silu:
+            y = torch.nn.functional.silu(y[:, :n_cols]) * y[:, n_cols:]
+        store(s0, c, y.to(torch.bfloat16))
+
+
+def grouped_gemm_fp8_block128(out, a_q, a_s, w_q, w_s, tile_off, counts,
+                              max_tiles, bm: int = 64):
+    """Reference for the plain stage of csrc/grouped_gemm_fp8_block.hip and
+    the CPU path: the padded-segment contract of `grouped_gemm_fp8` with the
+    arithmetic of `fp8_block_linear`, one rounding to bf16.
+
+        a_q [rows, K] e4m3, a_s [K/128, rows] f32   (rows in padded layout)
+        w_q [E, N, K] e4m3, w_s [E, N/128, K/128] f32
+        out [rows, N] bf16; padding rows are left untouched."""
+    def store(s0, c, y):
+        out[s0:s0 + c] = y.to(out.dtype)
+
+    _grouped_fp8_block128(a_q, a_s, w_q, w_s, None, tile_off, counts, bm,
+                          False, store)
+    return out
+
+
+def grouped_gemm_fp8_block128_gate_q(act_q, act_s, a_q, a_s, w_q, w_s,
+                                     row_tok, tile_off, counts, max_tiles,
+                                     bm: int = 64):
+    """Reference for stage 1 of csrc/grouped_gemm_fp8_block.hip and the CPU
+    path: gate/up through row_tok, SwiGLU in f32, one rounding to bf16, then
+    `quantize_rows_fp8_block128` of that — the stage-2 input, bit for bit
+    what a bf16 store followed by the separate quantiser gives.
+
+        a_q [T, K] e4m3, a_s [K/128, T] f32       (tokens; row_tok gathers)
+        w_q [E, 2I, K] e4m3 (gate rows first), w_s [E, 2I/128, K/128] f32
+        act_q [rows, I] e4m3, act_s [I/128, rows] f32 (padded layout);
+        padding rows are left untouched."""
+    def store(s0, c, y):
+        q, s = quantize_rows_fp8_block128(y)
+        act_q.view(torch.uint8)[s0:s0 + c] = q.view(torch.uint8)
+        act_s[:, s0:s0 + c] = s
+
+    _grouped_fp8_block128(a_q, a_s, w_q, w_s, row_tok, tile_off, counts, bm,
+                          True, store)
+    return act_q, act_s
+
+
 # the e2m1 grid, indexed by the 3 magnitude bits of a code (bit 3 = sign)
 E2M1_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
 
