@@ -77,7 +77,7 @@ void sutro_logit_penalties(void*, int, const int*, const int*, const int*,
                            const float*, const int*, const float*, int, int,
                            long, int, int, int, int, int, hipStream_t);
 void sutro_quant_rows_fp8(void*, float*, const void*, const int*, int, long,
-                          int, int, hipStream_t);
+                          int, int, int, hipStream_t);
 void sutro_grouped_gemm_fp8(void*, const void*, const float*, const void*,
                             const float*, const int*, const int*, const int*,
                             int, int, int, long, int, int, hipStream_t);
@@ -95,6 +95,9 @@ int sutro_gemm_tn_fp8_block_pipe_launch(void*, const void*, const float*,
 int sutro_gemm_tn_fp8_pipe_launch(void*, const void*, const float*,
                                   const void*, const float*, const void*, int,
                                   int, long, int, int, hipStream_t);
+int sutro_gemm_tn_fp8_skinny_launch(void*, const void*, const float*,
+                                    const void*, const float*, const void*,
+                                    int, int, long, int, hipStream_t);
 void sutro_grouped_gemm_fp8_block(void*, const void*, const float*, long,
                                   const void*, const float*, const int*,
                                   const int*, int, int, int, long, int,
@@ -476,6 +479,38 @@ torch::Tensor gemm_fp8_pipelined(torch::Tensor a_q, torch::Tensor a_scale,
   return out;
 }
 
+// gemm_fp8_pipelined's arithmetic for 1 <= M <= 256 on the weight-streaming
+// split-K kernel (csrc/gemm_tn_fp8_skinny.hip): the K sum runs in another
+// order, everything else is the same expression. N % 64 == 0, Kp % 128 == 0.
+// waves: 0 = the default of capture D2, or 4 / 8 (A/B only).
+torch::Tensor gemm_fp8_skinny(torch::Tensor a_q, torch::Tensor a_scale,
+                              torch::Tensor w_q, torch::Tensor w_scale,
+                              c10::optional<torch::Tensor> res, long waves) {
+  check_fp8_gemm_args(a_q, a_scale, w_q, w_scale);
+  const long M = a_q.size(0), Kp = a_q.size(1), N = w_q.size(0);
+  TORCH_CHECK(M <= 256, "gemm_fp8_skinny takes 1 <= M <= 256 (M=", M, ")");
+  TORCH_CHECK(N >= 64 && N % 64 == 0, "N must be a multiple of 64 (N=", N, ")");
+  TORCH_CHECK(waves == 0 || waves == 4 || waves == 8, "waves must be 0, 4, 8");
+  auto out = torch::empty({M, N}, a_q.options().dtype(at::kBFloat16));
+  const void* rp = nullptr;
+  if (res.has_value()) {
+    CHECK_CUDA(*res); CHECK_BF16(*res);
+    TORCH_CHECK(res->is_contiguous() && res->dim() == 2 &&
+                res->size(0) == M && res->size(1) == N, "res shape");
+    rp = res->data_ptr();
+  }
+  // the kernel's 16-byte operand and scale loads and 8-byte residual loads
+  for (const void* p : {a_q.data_ptr(), w_q.data_ptr(),
+                        (void*)w_scale.data_ptr<float>(), (void*)rp})
+    TORCH_CHECK(((uintptr_t)p & 15) == 0, "operands must be 16-byte aligned");
+  const int e = sutro_gemm_tn_fp8_skinny_launch(
+      out.data_ptr(), a_q.data_ptr(), a_scale.data_ptr<float>(),
+      w_q.data_ptr(), w_scale.data_ptr<float>(), rp, (int)M, (int)N, Kp,
+      waves ? (int)waves : 4, cur_stream());
+  TORCH_CHECK(e == 0, "gemm_fp8_skinny: unsupported arguments");
+  return out;
+}
+
 // out[M,I] = silu(g) * u, g / u the scaled products with the gate / up rows
 // of the merged w_q [2I, Kp]; f32 SwiGLU with one rounding (the grouped FP8
 // kernel's epilogue). I % 128 == 0.
@@ -784,11 +819,15 @@ void grouped_gemm(torch::Tensor out, torch::Tensor a, torch::Tensor w,
 
 // bf16 [R, K] -> e4m3 [R, Kp] + f32 scale [R] (Kp = K rounded up to 128, zero
 // tail). row_limit (int32 device scalar) * limit_mul bounds the rows written.
+// variant: -1 = the kernel the measured (R, K) rule picks, 0 = one wave per
+// row, 1 = one block per row; every variant writes the same bits.
 void quant_rows_fp8(torch::Tensor x, torch::Tensor out_q,
                     torch::Tensor out_scale,
-                    c10::optional<torch::Tensor> row_limit, long limit_mul) {
+                    c10::optional<torch::Tensor> row_limit, long limit_mul,
+                    long variant) {
   CHECK_CUDA(x); CHECK_CONTIG(x); CHECK_BF16(x);
   CHECK_CUDA(out_q); CHECK_CONTIG(out_q);
+  TORCH_CHECK(variant >= -1 && variant <= 1, "variant must be -1, 0 or 1");
   CHECK_CUDA(out_scale); CHECK_CONTIG(out_scale);
   TORCH_CHECK(x.dim() == 2 && out_q.dim() == 2, "x, out_q must be 2-D");
   TORCH_CHECK(is_fp8(out_q), "out_q must be float8_e4m3fn");
@@ -809,7 +848,7 @@ void quant_rows_fp8(torch::Tensor x, torch::Tensor out_q,
   }
   sutro_quant_rows_fp8(out_q.data_ptr(), out_scale.data_ptr<float>(),
                        x.data_ptr(), lim, (int)limit_mul, R, (int)K, (int)Kp,
-                       cur_stream());
+                       (int)variant, cur_stream());
 }
 
 void grouped_gemm_fp8(torch::Tensor out, torch::Tensor a_q,
@@ -1086,7 +1125,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("grouped_gemm", &grouped_gemm,
         "dropless MoE grouped GEMM (padded segments, static grid)");
   m.def("quant_rows_fp8", &quant_rows_fp8,
-        "bf16 rows -> e4m3 codes + f32 per-row scale (K padded to 128)");
+        "bf16 rows -> e4m3 codes + f32 per-row scale (K padded to 128)",
+        py::arg("x"), py::arg("out_q"), py::arg("out_scale"),
+        py::arg("row_limit") = c10::nullopt, py::arg("limit_mul") = 1,
+        py::arg("variant") = -1);
   m.def("grouped_gemm_fp8", &grouped_gemm_fp8,
         "dropless MoE grouped GEMM, e4m3 operands on the block-scaled MFMA");
   m.def("quant_weight_mxfp4", &quant_weight_mxfp4,
@@ -1117,6 +1159,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("a_q"), py::arg("a_scale"), py::arg("w_q"),
         py::arg("w_scale"), py::arg("res") = c10::nullopt,
         py::arg("xcd_swz") = 1);
+  m.def("gemm_fp8_skinny", &gemm_fp8_skinny,
+        "e4m3 W8A8 TN GEMM for M <= 256 (weight-streaming split-K MFMA)",
+        py::arg("a_q"), py::arg("a_scale"), py::arg("w_q"),
+        py::arg("w_scale"), py::arg("residual") = c10::nullopt,
+        py::arg("waves") = 0);
   m.def("gemm_fp8_gate_up_silu", &gemm_fp8_gate_up_silu,
         "SwiGLU fused into the pipelined e4m3 gate_up GEMM",
         py::arg("a_q"), py::arg("a_scale"), py::arg("w_q"),

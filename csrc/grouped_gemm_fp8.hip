@@ -121,13 +121,97 @@ __global__ void __launch_bounds__(256) quant_rows_fp8_kernel(
     *(u32x2*)(qr + c * 8) = u32x2{0u, 0u};
 }
 
+// Block-per-row variant for few, wide rows (the dense FP8 projections at
+// decode batch sizes): one block of up to 1024 threads per row, each thread
+// holding its QB_CACHE 8-element chunks in registers (rows of up to
+// 1024 * 8 * QB_CACHE = 32768 elements, one pass over memory where the wave
+// kernel above reads rows wider than 4096 twice). amax goes through the wave
+// reduction and one LDS round; max is order-independent and the scale and
+// convert expressions are the ones above, so the output is bit-identical.
+#define QB_CACHE 4
+#define QB_MAX_K (1024 * 8 * QB_CACHE)
+
+__global__ void __launch_bounds__(1024)
+__attribute__((target("no-packed-fp32-ops"))) quant_rows_fp8_block_kernel(
+    u8* __restrict__ out_q, float* __restrict__ out_scale,
+    const u16* __restrict__ x, const int* __restrict__ row_limit,
+    int limit_mul, long R, int K, int Kp) {
+  __shared__ float wmax[16];
+  const long row = blockIdx.x;
+  if (row_limit && row >= (long)row_limit[0] * limit_mul) return;
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  const u16* xr = x + row * K;
+  u8* qr = out_q + row * Kp;
+  const int nch = K >> 3;
+  const int nchp = Kp >> 3;
+
+  u16x8 v[QB_CACHE];
+  float amax = 0.f;
+#pragma unroll
+  for (int i = 0; i < QB_CACHE; ++i) {
+    const int c = i * nthr + tid;
+    v[i] = u16x8{0, 0, 0, 0, 0, 0, 0, 0};
+    if (c < nch) v[i] = *(const u16x8*)(xr + c * 8);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(bf2f(v[i][e])));
+  }
+  amax = wave_max_f32(amax);
+  if ((tid & 63) == 0) wmax[tid >> 6] = amax;
+  __syncthreads();
+  const int nw = nthr >> 6;
+  amax = wmax[0];
+  for (int i = 1; i < nw; ++i) amax = fmaxf(amax, wmax[i]);
+  const float scale = amax > 0.f ? amax / 448.0f : 1.0f;
+  if (tid == 0) out_scale[row] = scale;
+
+#pragma unroll
+  for (int i = 0; i < QB_CACHE; ++i) {
+    const int c = i * nthr + tid;
+    if (c >= nch) continue;
+    u32 w[2];
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      float f[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        f[e] = fminf(fmaxf(bf2f(v[i][p * 4 + e]) / scale, -448.0f), 448.0f);
+      w[p] = (u32)f2fp8x2(f[0], f[1]) | ((u32)f2fp8x2(f[2], f[3]) << 16);
+    }
+    *(u32x2*)(qr + c * 8) = u32x2{w[0], w[1]};
+  }
+  for (int c = nch + tid; c < nchp; c += nthr)
+    *(u32x2*)(qr + c * 8) = u32x2{0u, 0u};
+}
+
+// The (R, K) range in which the block-per-row kernel runs when the caller
+// leaves the choice open, from profiles/PROFILES.md capture D2 by the
+// project's routing margin: it cleared the margin at every measured R
+// (8 .. 256) for K = 8192 and 25600; at K = 5120 it missed it at R = 8, so
+// that width stays on the wave kernel.
+#define QB_AUTO_MAX_R 256
+#define QB_AUTO_MIN_K 8192
+
+// variant: -1 = the measured rule above, 0 = one wave per row, 1 = one block
+// per row (K <= QB_MAX_K, else the wave kernel runs).
 extern "C" void sutro_quant_rows_fp8(void* out_q, float* out_scale,
                                      const void* x, const int* row_limit,
                                      int limit_mul, long R, int K, int Kp,
-                                     hipStream_t stream) {
+                                     int variant, hipStream_t stream) {
   if (R == 0) return;
   // static grid, no host sync, no hipGetLastError: runs inside captured
   // decode steps
+  const bool block_row =
+      K <= QB_MAX_K && R < (1L << 31) &&
+      (variant == 1 ||
+       (variant < 0 && R <= QB_AUTO_MAX_R && K >= QB_AUTO_MIN_K));
+  if (block_row) {
+    // one 8-element chunk per thread up to 1024 threads, whole waves
+    const int thr = min(1024, ((K >> 3) + 63) / 64 * 64);
+    hipLaunchKernelGGL(quant_rows_fp8_block_kernel, dim3((unsigned)R),
+                       dim3(thr), 0, stream, (u8*)out_q, out_scale,
+                       (const u16*)x, row_limit, limit_mul, R, K, Kp);
+    return;
+  }
   hipLaunchKernelGGL(quant_rows_fp8_kernel, dim3((unsigned)((R + 3) / 4)),
                      dim3(256), 0, stream, (u8*)out_q, out_scale,
                      (const u16*)x, row_limit, limit_mul, R, K, Kp);

@@ -548,15 +548,18 @@ def grouped_gemm(out, a, w, row_tok, tile_off, counts, max_tiles, gate_silu,
                                   max_tiles, gate_silu, bm)
 
 
-def quantize_rows_fp8(x, out_q, out_scale, row_limit=None, limit_mul=1):
+def quantize_rows_fp8(x, out_q, out_scale, row_limit=None, limit_mul=1,
+                      variant=-1):
     """x [R, K] -> e4m3 codes out_q [R, Kp] + f32 per-row scale out_scale [R]
     (scale = amax/448, Kp = K rounded up to 128 with a zero tail):
     csrc/grouped_gemm_fp8.hip on GPU (bf16 input), torch reference on CPU —
     bit-identical. row_limit (int32 device scalar) * limit_mul optionally
-    bounds the rows written, without a host sync on GPU."""
+    bounds the rows written, without a host sync on GPU. variant picks the
+    GPU kernel (same bits from each): -1 the measured (R, K) rule, 0 one wave
+    per row, 1 one block per row."""
     if _use_hip(x):
         _require_hip().quant_rows_fp8(x, out_q, out_scale, row_limit,
-                                      limit_mul)
+                                      limit_mul, variant)
         return out_q, out_scale
     return torch_ref.quantize_rows_fp8(x, out_q, out_scale, row_limit,
                                        limit_mul)
@@ -590,17 +593,60 @@ def gate_up_silu_fp8_qualifies(two_i: int, k: int) -> bool:
     return two_i >= 256 and two_i % 256 == 0 and k >= 8 and k % 8 == 0
 
 
+# Routing of the dense FP8 projection between the 256-row kernel
+# (csrc/gemm_tn_fp8_pipe.hip) and the weight-streaming small-M kernel
+# (csrc/gemm_tn_fp8_skinny.hip): weight shape (N, Kp) -> max_M, the largest
+# token count up to which the skinny kernel beat the 256-row kernel at every
+# measured M by the margin of profiles/PROFILES.md capture D2 (median better
+# by more than twice the larger min-max spread). Shapes not listed were not
+# measured and stay on the 256-row kernel. A routed shape sums K in another
+# order at M <= max_M: same arithmetic, last-bit differences before the one
+# rounding.
+FP8_SKINNY_RULE: dict = {
+    (10240, 5120): 64,     # Qwen3-32B qkv
+    (5120, 8192): 64,      # Qwen3-32B o
+    (5120, 25600): 128,    # Qwen3-32B down
+}
+FP8_SKINNY_MAX_M = 256   # what the skinny kernel takes at all
+
+# SUTRO_FP8_SKINNY=1 forces the skinny kernel wherever it takes the shape
+# (M <= 256), =0 forces the 256-row kernel (A/B only); unset follows
+# FP8_SKINNY_RULE.
+_FP8_SKINNY_FORCE: Optional[bool] = {"1": True, "0": False}.get(
+    os.environ.get("SUTRO_FP8_SKINNY", ""))
+
+
+def set_linear_fp8_skinny(mode: Optional[bool]) -> None:
+    """In-process form of SUTRO_FP8_SKINNY: True / False force the path,
+    None restores the measured rule."""
+    global _FP8_SKINNY_FORCE
+    _FP8_SKINNY_FORCE = mode
+
+
+def linear_fp8_skinny_routed(n: int, kp: int, m: int) -> bool:
+    """Whether ops.linear_fp8 runs the skinny kernel for a [n, kp] weight at
+    m tokens."""
+    if m < 1 or m > FP8_SKINNY_MAX_M or _FP8_SKINNY_FORCE is False:
+        return False
+    if _FP8_SKINNY_FORCE:
+        return True
+    return m <= FP8_SKINNY_RULE.get((n, kp), 0)
+
+
 def linear_fp8(x, w_q, w_scale, residual=None):
     """Dense W8A8 projection: x [T, K] (bf16 on GPU) through w_q [N, Kp] e4m3
     with f32 per-output-channel scales w_scale [N]; returns [T, N] in x's
     dtype, optionally + residual (added in f32 before the one rounding).
     Arithmetic: torch_ref.linear_fp8. On GPU the row quantiser runs as its
-    own pass, then csrc/gemm_tn_fp8_pipe.hip; no host sync, every tensor from
+    own pass, then csrc/gemm_tn_fp8_pipe.hip, or csrc/gemm_tn_fp8_skinny.hip
+    where `linear_fp8_skinny_routed` says so; no host sync, every tensor from
     the caching allocator."""
     if _use_hip(x):
         C = _require_hip()
         # fresh caching-allocator tensors: safe under hipGraph capture
         x_q, x_s = torch_ref.quantize_act_fp8(x, quantize_rows_fp8)
+        if linear_fp8_skinny_routed(w_q.shape[0], w_q.shape[1], x.shape[0]):
+            return C.gemm_fp8_skinny(x_q, x_s, w_q, w_scale, residual)
         return C.gemm_fp8_pipelined(x_q, x_s, w_q, w_scale, residual)
     return torch_ref.linear_fp8(x, w_q, w_scale, residual)
 

@@ -11,7 +11,14 @@ Per Qwen3-32B projection shape and token count M it times
   (d) the 128-wide group quantiser (ops.quantize_rows_fp8_block128),
   (e) the block-scaled GEMM on pre-quantised operands,
 and reports TF/s of (b), (c) and (e) and the ratios (a + b) / c, (d + e) / c
-and (d + e) / (a + b).
+and (d + e) / (a + b). For the plain projections at M <= 256 it also times
+  (f) the weight-streaming small-M GEMM (csrc/gemm_tn_fp8_skinny.hip) with 4
+      and with 8 waves per block,
+  (g) the block-per-row variant of the row quantiser ((a) is the wave-per-row
+      kernel, both forced),
+  (h) a device copy of the weight codes, the same bytes (f) has to stream,
+and reports (g + f) / c with the faster of the two (f) and the weight bytes
+per second of (f) beside the copy's.
 
 Method of tools/bench_gate_up.py: variants alternate round by round; each
 round times a window of back-to-back calls per variant; median (min-max)
@@ -21,6 +28,7 @@ no call finds its weights in the last-level cache; the TunableOp table is
 loaded the way the engine loads it.
 
     python tools/bench_dense_fp8.py [--rounds 5] [--calls 10] [--m 64,2048]
+                                    [--shapes qkv,o,down]
 Writes bench_outputs/dense_fp8_bench.csv (or under $BENCH_OUT)."""
 
 import argparse
@@ -74,8 +82,11 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--calls", type=int, default=10)
     ap.add_argument("--m", type=str, default=None, metavar="M,M,..")
+    ap.add_argument("--shapes", type=str, default=None, metavar="LABEL,..")
     args = ap.parse_args()
     ms = [int(m) for m in args.m.split(",")] if args.m else MS
+    shapes = [s for s in SHAPES
+              if not args.shapes or s[0] in args.shapes.split(",")]
 
     _setup_tunableop(EngineConfig(spec=get_model_spec("qwen-3-32b"),
                                   device="cuda"))
@@ -87,8 +98,13 @@ def main():
             "block_quant_us,block_gemm_us,block_quant_min_us,"
             "block_quant_max_us,block_gemm_min_us,block_gemm_max_us,"
             "block_gemm_tflops,ratio_block_over_bf16,"
-            "ratio_block_over_per_channel"]
-    for label, N, K in SHAPES:
+            "ratio_block_over_per_channel,"
+            "skinny4_us,skinny8_us,rowquant_us,copy_us,skinny4_min_us,"
+            "skinny4_max_us,skinny8_min_us,skinny8_max_us,rowquant_min_us,"
+            "rowquant_max_us,copy_min_us,copy_max_us,"
+            "ratio_rowquant_plus_skinny_over_bf16,skinny_weight_gbps,"
+            "copy_gbps"]
+    for label, N, K in shapes:
         g = torch.Generator(device="cuda")
         g.manual_seed(N + K)
         ws = [(torch.randn(N, K, device="cuda", generator=g) / K ** 0.5)
@@ -120,13 +136,23 @@ def main():
                     F.linear(xs[i], ws[i])
 
             def quant(i):
-                ops.quantize_rows_fp8(xs[i], *xq[i])
+                ops.quantize_rows_fp8(xs[i], *xq[i], None, 1, 0)
 
             def bquant(i):
                 ops.quantize_rows_fp8_block128(xs[i])
 
             vs = [("quant", quant), ("fp8", fp8), ("bf16", bf16),
                   ("bquant", bquant), ("blk", blk)]
+            skinny = label != "gate_up" and M <= ops.FP8_SKINNY_MAX_M
+            if skinny:
+                wcopy = torch.empty_like(wq[0][0])
+                vs += [("sk4", lambda i: _C.gemm_fp8_skinny(
+                            *xq[i], *wq[i], None, 4)),
+                       ("sk8", lambda i: _C.gemm_fp8_skinny(
+                            *xq[i], *wq[i], None, 8)),
+                       ("rquant", lambda i: ops.quantize_rows_fp8(
+                            xs[i], *xq[i], None, 1, 1)),
+                       ("copy", lambda i: wcopy.copy_(wq[i][0]))]
             times = {name: [] for name, _ in vs}
             for r in range(args.rounds + 1):  # round 0 warms up
                 for name, fn in vs:
@@ -135,6 +161,7 @@ def main():
                         times[name].append(t)
             med = {n: statistics.median(t) for n, t in times.items()}
             flops = 2.0 * M * N * K
+            Kp = torch_ref.fp8_padded_k(K)
             ratio = (med["quant"] + med["fp8"]) / med["bf16"]
             bratio = (med["bquant"] + med["blk"]) / med["bf16"]
             bover = (med["bquant"] + med["blk"]) / (med["quant"] + med["fp8"])
@@ -148,7 +175,16 @@ def main():
                 f"{med['bquant']:.1f},{med['blk']:.1f},"
                 + ",".join(f"{f(times[n]):.1f}" for n in ("bquant", "blk")
                            for f in (min, max))
-                + f",{flops / med['blk'] / 1e6:.1f},{bratio:.3f},{bover:.3f}")
+                + f",{flops / med['blk'] / 1e6:.1f},{bratio:.3f},{bover:.3f}"
+                + ("," * 15 if not skinny else
+                   "," + ",".join(f"{med[n]:.1f}" for n in
+                                  ("sk4", "sk8", "rquant", "copy"))
+                   + "," + ",".join(f"{f(times[n]):.1f}" for n in
+                                    ("sk4", "sk8", "rquant", "copy")
+                                    for f in (min, max))
+                   + f",{(med['rquant'] + min(med['sk4'], med['sk8'])) / med['bf16']:.3f}"
+                   f",{N * Kp / min(med['sk4'], med['sk8']) / 1e3:.0f}"
+                   f",{N * Kp / med['copy'] / 1e3:.0f}"))
             print(f"{label:8s} M={M:6d} N={N} K={K}: quant {med['quant']:8.1f}"
                   f" us  fp8 {med['fp8']:9.1f} us ({flops / med['fp8'] / 1e6:7.1f}"
                   f" TF/s)  bf16 {med['bf16']:9.1f} us "
@@ -157,6 +193,21 @@ def main():
                   f"{med['blk']:9.1f} us ({flops / med['blk'] / 1e6:7.1f} TF/s)"
                   f"  (d+e)/c {bratio:.3f}  (d+e)/(a+b) {bover:.3f}",
                   flush=True)
+            if skinny:
+                sk = min(med["sk4"], med["sk8"])
+                print(f"{'':8s} skinny: 4 waves {med['sk4']:7.1f} us "
+                      f"({min(times['sk4']):.1f}-{max(times['sk4']):.1f})  "
+                      f"8 waves {med['sk8']:7.1f} us "
+                      f"({min(times['sk8']):.1f}-{max(times['sk8']):.1f})  "
+                      f"fp8 ({min(times['fp8']):.1f}-{max(times['fp8']):.1f})"
+                      f"  row quant {med['rquant']:6.1f} us "
+                      f"({min(times['rquant']):.1f}-{max(times['rquant']):.1f})"
+                      f" vs {med['quant']:6.1f} "
+                      f"({min(times['quant']):.1f}-{max(times['quant']):.1f})"
+                      f"  (g+f)/c {(med['rquant'] + sk) / med['bf16']:.3f}  "
+                      f"weights {N * Kp / sk / 1e3:.0f} GB/s, copy "
+                      f"{med['copy']:.1f} us = {N * Kp / med['copy'] / 1e3:.0f}"
+                      " GB/s", flush=True)
             del xs, xq, xb
         del ws, wq, wb
         torch.cuda.empty_cache()
