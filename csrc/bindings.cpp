@@ -72,6 +72,8 @@ void sutro_grouped_gemm(void*, const void*, const void*, const int*,
                         int, hipStream_t);
 void sutro_moe_combine(void*, const void*, const long*, const float*, int,
                        int, int, hipStream_t);
+int sutro_moe_route(const void*, int, int*, float*, long*, int*, int*, int*,
+                    int*, int*, int, int, int, int, int, int, hipStream_t);
 void sutro_logit_penalties(void*, int, const int*, const int*, const int*,
                            const int*, const int*, const float*, const float*,
                            const float*, const int*, const float*, int, int,
@@ -989,6 +991,58 @@ void moe_combine(torch::Tensor out, torch::Tensor rows, torch::Tensor padpos,
                     (int)h, (int)k, cur_stream());
 }
 
+// fused MoE routing (csrc/moe_route.hip): logits [T, E] -> idx / w / padpos
+// [T, k], row_tok [rows_max], tile_off [E_l + 1], counts [E_l]; blk_hist /
+// blk_base are scratch, one row of E_l per 128-token block
+void moe_route(torch::Tensor logits, long top_k, long expert_base,
+               long experts_local, long bm, torch::Tensor idx,
+               torch::Tensor w, torch::Tensor padpos, torch::Tensor row_tok,
+               torch::Tensor tile_off, torch::Tensor counts,
+               torch::Tensor blk_hist, torch::Tensor blk_base) {
+  CHECK_CUDA(logits); CHECK_CONTIG(logits);
+  const bool f32 = logits.scalar_type() == at::kFloat;
+  TORCH_CHECK(f32 || logits.scalar_type() == at::kBFloat16,
+              "logits must be bf16 or f32");
+  TORCH_CHECK(logits.dim() == 2 && logits.size(0) > 0, "logits must be [T, E]");
+  const long T = logits.size(0), E = logits.size(1), k = top_k;
+  const long E_l = experts_local;
+  TORCH_CHECK((E >= 1 && E <= 16) || E == 32 || E == 64 || E == 128,
+              "moe_route takes up to 16, or 32, 64 or 128 experts, got ", E);
+  TORCH_CHECK(k >= 1 && k <= 8 && k <= E, "moe_route takes top_k 1..8, got ",
+              k);
+  TORCH_CHECK(bm == 64 || bm == 128, "moe_route takes bm 64 or 128, got ", bm);
+  TORCH_CHECK(E_l >= 1 && expert_base >= 0 && expert_base + E_l <= E,
+              "local experts [", expert_base, ", ", expert_base + E_l,
+              ") outside the ", E, " experts");
+  TORCH_CHECK(T * k + E_l * bm <= INT_MAX, "T * top_k too large");
+  TORCH_CHECK((uintptr_t)logits.data_ptr() % 16 == 0,
+              "logits must be 16-byte aligned");
+  const long rows_max = T * k + E_l * bm, nblk = (T + 127) / 128;
+  for (const torch::Tensor* t : {&idx, &w, &padpos, &row_tok, &tile_off,
+                                 &counts, &blk_hist, &blk_base}) {
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous(),
+                "moe_route buffers must be contiguous GPU tensors");
+    TORCH_CHECK(t == &w ? t->scalar_type() == at::kFloat
+                : t == &padpos ? t->scalar_type() == at::kLong
+                               : t->scalar_type() == at::kInt,
+                "moe_route buffers: w f32, padpos int64, the rest int32");
+  }
+  TORCH_CHECK(idx.numel() >= T * k && w.numel() >= T * k
+              && padpos.numel() >= T * k, "idx / w / padpos hold T * top_k");
+  TORCH_CHECK(row_tok.numel() >= rows_max, "row_tok too short");
+  TORCH_CHECK(tile_off.numel() >= E_l + 1 && counts.numel() >= E_l,
+              "tile_off / counts too short");
+  TORCH_CHECK(blk_hist.numel() >= nblk * E_l && blk_base.numel() >= nblk * E_l,
+              "blk_hist / blk_base hold ceil(T / 128) * experts_local");
+  const int e = sutro_moe_route(
+      logits.data_ptr(), f32 ? 1 : 0, idx.data_ptr<int>(),
+      w.data_ptr<float>(), padpos.data_ptr<long>(), row_tok.data_ptr<int>(),
+      tile_off.data_ptr<int>(), counts.data_ptr<int>(),
+      blk_hist.data_ptr<int>(), blk_base.data_ptr<int>(), (int)T, (int)E,
+      (int)k, (int)expert_base, (int)E_l, (int)bm, cur_stream());
+  TORCH_CHECK(e == 0, "moe_route: unsupported shape");
+}
+
 void sampler_fused(torch::Tensor logits, torch::Tensor temps,
                    torch::Tensor topps, torch::Tensor topks, torch::Tensor us,
                    c10::optional<torch::Tensor> mask, long vl,
@@ -1122,6 +1176,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mfma16_probe", &mfma16_probe, "16x16 MFMA fragment-layout probe");
   m.def("hd64_stage_probe", &hd64_stage_probe, "D=64 decode stage dump probe");
   m.def("moe_combine", &moe_combine, "fused MoE weighted gather-combine");
+  m.def("moe_route", &moe_route,
+        "fused MoE routing: top-k select + segment layout");
   m.def("grouped_gemm", &grouped_gemm,
         "dropless MoE grouped GEMM (padded segments, static grid)");
   m.def("quant_rows_fp8", &quant_rows_fp8,

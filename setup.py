@@ -31,6 +31,7 @@ SOURCES = [
     "csrc/grouped_gemm_fp8.hip",
     "csrc/grouped_gemm_fp8_block.hip",
     "csrc/grouped_gemm_mxfp4.hip",
+    "csrc/moe_route.hip",
     "csrc/logit_penalties.hip",
 ]
 

@@ -194,6 +194,10 @@ def models():
                    "mxfp4 stores 4.25 bits per weight, fp8_block128 is "
                    "fp8 with the 128x128 block scales of the published FP8 "
                    "checkpoints)")
+@click.option("--moe-routing", default="torch",
+              type=click.Choice(["torch", "fused"]),
+              help="MoE routing glue: library ops, or the fused top-k select "
+                   "+ segment layout kernels (ties go to the lower expert)")
 @click.option("--dense-weight-dtype", default="bf16",
               type=click.Choice(["bf16", "fp8_e4m3", "fp8_block128"]),
               help="storage of the dense projections (qkv, o, gate_up, down; "
@@ -204,13 +208,15 @@ def models():
               help="run sliding-window layers with their window and "
                    "attention sinks where the model has them (gpt-oss)")
 def serve(host: str, port: int, device: str, moe_weight_dtype: str,
-          dense_weight_dtype: str, local_attention: bool):
+          moe_routing: str, dense_weight_dtype: str, local_attention: bool):
     """Serve the HTTP API (the same endpoint contract as api.sutro.sh)."""
     from .service.http_api import run_server
 
     engine_kwargs = {}
     if moe_weight_dtype != "bf16":
         engine_kwargs["moe_weight_dtype"] = moe_weight_dtype
+    if moe_routing != "torch":
+        engine_kwargs["moe_routing"] = moe_routing
     if dense_weight_dtype != "bf16":
         engine_kwargs["dense_weight_dtype"] = dense_weight_dtype
     if local_attention:

@@ -105,8 +105,20 @@ class EngineConfig:
     # causal attention without a sinks parameter, as before. Ignored for
     # specs with neither (a service hands one engine_kwargs to every model).
     local_attention: bool = False
+    # how a MoE layer turns router logits into the grouped kernels' shaping
+    # tensors: "torch" with library ops (softmax, topk, a stable sort,
+    # scatters), "fused" with the three kernels of csrc/moe_route.hip
+    # (docs/ENGINE.md, "MoE routing"). "fused" selects on the logits with ties
+    # to the lower expert index, where torch.topk leaves ties unspecified, so
+    # the two can pick different experts on tied logits. Ignored for specs
+    # without experts.
+    moe_routing: str = "torch"
 
     def __post_init__(self) -> None:
+        if self.moe_routing not in ("torch", "fused"):
+            raise ValueError(
+                f"moe_routing must be 'torch' or 'fused', "
+                f"got {self.moe_routing!r}")
         if self.prefix_decode not in ("per_row", "shared"):
             raise ValueError(
                 f"prefix_decode must be 'per_row' or 'shared', "

@@ -87,7 +87,8 @@ class LLMEngine:
             with torch.device(cfg.device):
                 model = Qwen3Model(self.spec, cfg.dtype, cfg.max_model_len,
                                    self.tp, moe_ep=cfg.moe_ep,
-                                   local_attention=cfg.local_attention)
+                                   local_attention=cfg.local_attention,
+                                   moe_routing=cfg.moe_routing)
             if cfg.weights_path:
                 from ..models.loader import load_weights
 

@@ -300,7 +300,8 @@ class Qwen3MoE(nn.Module):
     static shaping; per-expert segment loop as the CPU reference."""
 
     def __init__(self, spec: ModelSpec, dtype: torch.dtype,
-                 tp: Optional[TPContext] = None, ep: bool = False):
+                 tp: Optional[TPContext] = None, ep: bool = False,
+                 moe_routing: str = "torch"):
         """Two parallelization modes over the same group:
         - tp (default): every rank holds ALL experts with the intermediate
           dim sharded (like the dense MLP).
@@ -309,11 +310,18 @@ class Qwen3MoE(nn.Module):
           the per-block all-reduce combines — the natural expert-parallel
           form for lockstep TP engines on the fully-connected xGMI mesh
           (token-sharded all-to-all dispatch applies only when ranks hold
-          different tokens, which lockstep groups do not)."""
+          different tokens, which lockstep groups do not).
+
+        moe_routing (EngineConfig.moe_routing): "torch" turns router logits
+        into the grouped kernels' shaping tensors with library ops; "fused"
+        does it with ops.moe_route (csrc/moe_route.hip), whose selection
+        breaks ties towards the lower expert index."""
         super().__init__()
         tp = tp or TPContext()
         self.tp = tp
         self.ep = ep and tp.size > 1
+        self.moe_routing = moe_routing
+        self._route_warned = False
         self.num_experts = spec.num_experts
         self.top_k = spec.experts_per_token
         h, m = spec.hidden_size, spec.moe_intermediate_size
@@ -578,7 +586,13 @@ class Qwen3MoE(nn.Module):
     def _forward_loop(self, x: torch.Tensor) -> torch.Tensor:
         """Exact segment-per-expert execution (CPU reference path)."""
         T, h = x.shape
-        weights, idx = torch_ref.topk_softmax_router(self.router(x), self.top_k)
+        if self.moe_routing == "fused":
+            # the fused routing's selection, so CPU and GPU agree on ties
+            weights, idx = torch_ref.moe_route_select(self.router(x),
+                                                      self.top_k)
+        else:
+            weights, idx = torch_ref.topk_softmax_router(self.router(x),
+                                                         self.top_k)
         flat_expert = idx.reshape(-1)                      # [T*k]
         flat_tok = torch.arange(T, device=x.device).repeat_interleave(self.top_k)
         order = torch.argsort(flat_expert, stable=True)
@@ -723,6 +737,12 @@ class Qwen3MoE(nn.Module):
                 "row_tok": torch.empty(rows_max, dtype=torch.int32,
                                        device=dev),
             }
+            # the fused routing's outputs and scratch (row_tok above is the
+            # longer of the two and serves both routings)
+            for name, buf in ops.moe_route_workspace(
+                    T, self.top_k, self.experts_per_rank, dev,
+                    self._GG_BM).items():
+                ws.setdefault(name, buf)
             ws["out"] = torch.empty(T, h, dtype=dtype, device=dev)
             if fp8:
                 # quantised stage inputs + their per-row scales
@@ -832,39 +852,13 @@ class Qwen3MoE(nn.Module):
         BM = 128 if T * k >= E_l * 256 else 64
         dev = x.device
         ws = self._workspace(T, dev)
-        weights, idx = torch_ref.topk_softmax_router(self.router(x), k)
-        flat_e = idx.reshape(-1)                          # [T*k]
-        flat_tok = torch.arange(T, device=dev).repeat_interleave(k)
-        order = torch.argsort(flat_e, stable=True)
-        sorted_e = flat_e[order]
-        sorted_tok = flat_tok[order]
-        e_loc = sorted_e - base
-        valid = (e_loc >= 0) & (e_loc < E_l)              # EP: local only
-        # capture-clean counting: bincount and boolean-mask indexing host-
-        # sync (output size), which silently broke hipGraph capture of MoE
-        # decode steps — every shaping op below is static-shaped
-        counts = torch.zeros(E_l, dtype=torch.int32, device=dev)
-        counts.index_add_(0, e_loc.clamp(0, E_l - 1),
-                          valid.to(torch.int32))
-        padded = (counts + (BM - 1)) // BM * BM
-        pad_off = torch.zeros(E_l + 1, dtype=torch.int32, device=dev)
-        pad_off[1:] = torch.cumsum(padded, 0)
-        tile_off = pad_off // BM
-        # rank of each assignment within its expert segment
-        first = torch.searchsorted(sorted_e, sorted_e, side="left")
-        pos = torch.arange(T * k, device=dev) - first
         rows_max = T * k + E_l * BM                       # static bound
-        row_tok = ws["row_tok"][:rows_max]
-        row_tok.fill_(-1)
-        padpos_sorted = (pad_off[e_loc.clamp(0, E_l - 1).long()].long()
-                         + pos)
-        # invalid (non-local EP) assignments redirect to the last slot,
-        # which lies beyond every padded segment (padded_total < rows_max)
-        # so no tile ever reads it — scatter_ keeps shapes static
-        padpos_sorted = torch.where(valid, padpos_sorted,
-                                    torch.full_like(padpos_sorted,
-                                                    rows_max - 1))
-        row_tok.scatter_(0, padpos_sorted, sorted_tok.to(torch.int32))
+        if self._use_fused_routing(BM):
+            w_flat, pp, row_tok, tile_off, counts = ops.moe_route(
+                self.router(x), k, base, E_l, BM, ws)
+        else:
+            w_flat, pp, row_tok, tile_off, counts = self._route_torch(
+                self.router(x), ws, BM)
         max_tiles = rows_max // BM
 
         m_l = self.gate_up.shape[1] // 2
@@ -915,16 +909,7 @@ class Qwen3MoE(nn.Module):
                              max_tiles, True, bm=BM)
             ops.grouped_gemm(out_sorted, act, self.down, None, tile_off,
                              counts, max_tiles, False, bm=BM)
-        # deterministic combine in fixed k-order (no float atomics): map each
-        # original (token, j) assignment back to its padded row
-        padpos = torch.empty(T * k, dtype=torch.long, device=dev)
-        padpos[order] = padpos_sorted
-        w_flat = weights.reshape(-1).clone()
-        inv_valid = torch.zeros(T * k, dtype=torch.bool, device=dev)
-        inv_valid[order] = valid
-        w_flat = torch.where(inv_valid, w_flat,
-                             torch.zeros_like(w_flat)).view(T, k)
-        pp = padpos.view(T, k)
+
         if x.is_cuda:
             # fused weighted gather-combine into the workspace (no allocs
             # inside captured decode steps)
@@ -935,18 +920,89 @@ class Qwen3MoE(nn.Module):
         contrib = out_sorted[pp].float()
         return (contrib * w_flat.view(T, k, 1)).sum(dim=1).to(x.dtype)
 
+    def _use_fused_routing(self, bm: int) -> bool:
+        """moe_routing == "fused" and csrc/moe_route.hip takes the shape; a
+        shape it does not take warns once and keeps the torch glue."""
+        if self.moe_routing != "fused":
+            return False
+        if ops.moe_route_supported(self.num_experts, self.top_k, bm):
+            return True
+        if not self._route_warned:
+            import warnings
+
+            warnings.warn(
+                f"moe_routing='fused' takes up to 16, or 32/64/128 experts "
+                f"and top_k <= 8; this layer has {self.num_experts} experts, "
+                f"top_k {self.top_k}: using the torch routing")
+            self._route_warned = True
+        return False
+
+    def _route_torch(self, logits: torch.Tensor, ws: dict, BM: int):
+        """Router logits -> (w [T,k], padpos [T,k], row_tok, tile_off,
+        counts) with library ops (moe_routing="torch"): softmax + topk, a
+        stable sort by expert, static-shaped counting and scatters."""
+        T = logits.shape[0]
+        k = self.top_k
+        E_l, base = self.experts_per_rank, self.expert_base
+        dev = logits.device
+        weights, idx = torch_ref.topk_softmax_router(logits, k)
+        flat_e = idx.reshape(-1)                          # [T*k]
+        flat_tok = torch.arange(T, device=dev).repeat_interleave(k)
+        order = torch.argsort(flat_e, stable=True)
+        sorted_e = flat_e[order]
+        sorted_tok = flat_tok[order]
+        e_loc = sorted_e - base
+        valid = (e_loc >= 0) & (e_loc < E_l)              # EP: local only
+        # capture-clean counting: bincount and boolean-mask indexing host-
+        # sync (output size), which silently broke hipGraph capture of MoE
+        # decode steps — every shaping op below is static-shaped
+        counts = torch.zeros(E_l, dtype=torch.int32, device=dev)
+        counts.index_add_(0, e_loc.clamp(0, E_l - 1),
+                          valid.to(torch.int32))
+        padded = (counts + (BM - 1)) // BM * BM
+        pad_off = torch.zeros(E_l + 1, dtype=torch.int32, device=dev)
+        pad_off[1:] = torch.cumsum(padded, 0)
+        tile_off = pad_off // BM
+        # rank of each assignment within its expert segment
+        first = torch.searchsorted(sorted_e, sorted_e, side="left")
+        pos = torch.arange(T * k, device=dev) - first
+        rows_max = T * k + E_l * BM                       # static bound
+        row_tok = ws["row_tok"][:rows_max]
+        row_tok.fill_(-1)
+        padpos_sorted = (pad_off[e_loc.clamp(0, E_l - 1).long()].long()
+                         + pos)
+        # invalid (non-local EP) assignments redirect to the last slot,
+        # which lies beyond every padded segment (padded_total < rows_max)
+        # so no tile ever reads it — scatter_ keeps shapes static
+        padpos_sorted = torch.where(valid, padpos_sorted,
+                                    torch.full_like(padpos_sorted,
+                                                    rows_max - 1))
+        row_tok.scatter_(0, padpos_sorted, sorted_tok.to(torch.int32))
+        # deterministic combine in fixed k-order (no float atomics): map each
+        # original (token, j) assignment back to its padded row
+        padpos = torch.empty(T * k, dtype=torch.long, device=dev)
+        padpos[order] = padpos_sorted
+        w_flat = weights.reshape(-1).clone()
+        inv_valid = torch.zeros(T * k, dtype=torch.bool, device=dev)
+        inv_valid[order] = valid
+        w_flat = torch.where(inv_valid, w_flat,
+                             torch.zeros_like(w_flat)).view(T, k)
+        pp = padpos.view(T, k)
+        return w_flat, pp, row_tok, tile_off, counts
+
 
 class Qwen3Block(nn.Module):
     def __init__(self, spec: ModelSpec, dtype: torch.dtype, layer_idx: int,
                  tp: Optional[TPContext] = None, moe_ep: bool = False,
-                 local_attention: bool = False):
+                 local_attention: bool = False, moe_routing: str = "torch"):
         super().__init__()
         self.input_layernorm = RMSNorm(spec.hidden_size, spec.rms_eps, dtype)
         self.self_attn = Qwen3Attention(spec, dtype, layer_idx, tp,
                                         local_attention)
         self.post_attention_layernorm = RMSNorm(spec.hidden_size, spec.rms_eps, dtype)
         if spec.num_experts > 0:
-            self.mlp = Qwen3MoE(spec, dtype, tp, ep=moe_ep)
+            self.mlp = Qwen3MoE(spec, dtype, tp, ep=moe_ep,
+                                moe_routing=moe_routing)
         else:
             self.mlp = Qwen3MLP(spec.hidden_size, spec.intermediate_size, dtype, tp)
 
@@ -972,7 +1028,7 @@ class Qwen3Model(nn.Module):
 
     def __init__(self, spec: ModelSpec, dtype: torch.dtype, max_len: int,
                  tp: Optional[TPContext] = None, moe_ep: bool = False,
-                 local_attention: bool = False):
+                 local_attention: bool = False, moe_routing: str = "torch"):
         super().__init__()
         self.spec = spec
         self.tp = tp or TPContext()
@@ -981,7 +1037,8 @@ class Qwen3Model(nn.Module):
                                     and spec.has_local_attention)
         self.embed_tokens = nn.Embedding(spec.vocab_size, spec.hidden_size, dtype=dtype)
         self.layers = nn.ModuleList(
-            [Qwen3Block(spec, dtype, i, self.tp, moe_ep, self.local_attention)
+            [Qwen3Block(spec, dtype, i, self.tp, moe_ep, self.local_attention,
+                        moe_routing)
              for i in range(spec.num_layers)]
         )
         self.norm = RMSNorm(spec.hidden_size, spec.rms_eps, dtype)

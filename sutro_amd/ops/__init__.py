@@ -817,6 +817,68 @@ def moe_combine(out, rows, padpos, w):
     return out
 
 
+# tokens one block of csrc/moe_route.hip owns (sizes the per-block scratch)
+MOE_ROUTE_BLOCK_TOKENS = 128
+
+
+def moe_route_supported(num_experts: int, top_k: int, bm: int) -> bool:
+    """shapes csrc/moe_route.hip takes"""
+    return ((1 <= num_experts <= 16 or num_experts in (32, 64, 128))
+            and 1 <= top_k <= min(8, num_experts) and bm in (64, 128))
+
+
+def moe_route_workspace(max_tokens: int, top_k: int, experts_local: int,
+                        device, bm: int = 128) -> dict:
+    """Buffers of `moe_route` for up to max_tokens tokens: its outputs and
+    its scratch (selected experts, per-block expert tallies and bases).
+    Qwen3MoE._workspace merges them into the shared MoE workspace, so they
+    exist before hipGraph capture."""
+    tk = max_tokens * top_k
+    nblk = -(-max_tokens // MOE_ROUTE_BLOCK_TOKENS)
+
+    def i32(n):
+        return torch.empty(n, dtype=torch.int32, device=device)
+
+    return {
+        "route_idx": i32(tk),
+        "route_w": torch.empty(tk, dtype=torch.float32, device=device),
+        "route_padpos": torch.empty(tk, dtype=torch.long, device=device),
+        "route_tile_off": i32(experts_local + 1),
+        "route_counts": i32(experts_local),
+        "route_blk_hist": i32(nblk * experts_local),
+        "route_blk_base": i32(nblk * experts_local),
+        "row_tok": i32(tk + experts_local * bm),
+    }
+
+
+def moe_route(logits, top_k: int, expert_base: int, experts_local: int,
+              bm: int, ws: Optional[dict] = None):
+    """Router logits [T, E] -> (w [T,k] f32, padpos [T,k] i64, row_tok
+    [T*k + E_l*bm] i32, tile_off [E_l+1] i32, counts [E_l] i32): top-k
+    selection, weights and the padded per-expert segment layout in three
+    launches of csrc/moe_route.hip (static shapes, no host sync, bits
+    independent of scheduling). Semantics: torch_ref.moe_route, which is
+    also the CPU path. On GPU the results are views into `ws`
+    (`moe_route_workspace`; allocated here when None), overwritten by the
+    next call on the same workspace; ws["route_idx"][:T*k] holds the
+    selected experts."""
+    if not _use_hip(logits):
+        return torch_ref.moe_route(logits, top_k, expert_base, experts_local,
+                                   bm)
+    T = logits.shape[0]
+    if ws is None:
+        ws = moe_route_workspace(T, top_k, experts_local, logits.device, bm)
+    tk = T * top_k
+    w, padpos = ws["route_w"][:tk], ws["route_padpos"][:tk]
+    row_tok = ws["row_tok"][:tk + experts_local * bm]
+    _require_hip().moe_route(logits, top_k, expert_base, experts_local, bm,
+                             ws["route_idx"], w, padpos, row_tok,
+                             ws["route_tile_off"], ws["route_counts"],
+                             ws["route_blk_hist"], ws["route_blk_base"])
+    return (w.view(T, top_k), padpos.view(T, top_k), row_tok,
+            ws["route_tile_off"], ws["route_counts"])
+
+
 # largest hist_len + bias width one LDS table (16384 entries, half full) holds
 PENALTY_MAX_ENTRIES = 8192
 

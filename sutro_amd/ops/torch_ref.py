@@ -161,6 +161,69 @@ def topk_softmax_router(
     return w, idx
 
 
+def moe_route_select(logits: torch.Tensor, top_k: int):
+    """The selection of `moe_route`: (weights [T,k] fp32, indices [T,k]
+    int64). Per token the k largest LOGITS compared as f32, ties to the lower
+    expert index, slot j the j-th largest; w_j = exp(l_j - l_max) / sum over
+    the k selected — softmax then top-k renormalisation with the full-row
+    denominator cancelled."""
+    vals, idx = torch.sort(logits.float(), dim=-1, descending=True,
+                           stable=True)
+    vals, idx = vals[:, :top_k], idx[:, :top_k]
+    ex = torch.exp(vals - vals[:, :1])
+    return ex / ex.sum(dim=-1, keepdim=True), idx
+
+
+def moe_route(logits: torch.Tensor, top_k: int, expert_base: int,
+              experts_local: int, bm: int):
+    """Statement of the fused MoE routing (csrc/moe_route.hip) and its CPU
+    path: router logits [T, E] -> (w [T,k] f32, padpos [T,k] i64, row_tok
+    [rows_max] i32, tile_off [E_l+1] i32, counts [E_l] i32), rows_max =
+    T*k + E_l*bm — the tensors Qwen3MoE._forward_grouped hands to the grouped
+    GEMMs and moe_combine.
+
+    Selection and weights: `moe_route_select`. `topk_softmax_router` selects
+    with torch.topk on the probabilities and leaves ties unspecified; router
+    logits are bf16, so ties at the k-th place are common, and the two can
+    pick different experts there. That is why this routing is a setting of
+    its own (`moe_routing="fused"`) and not a replacement.
+
+    Layout: assignments (t, j) ordered by (expert, t*k + j); counts over the
+    local experts [expert_base, expert_base + E_l) only; segments padded to
+    bm, tile_off = exclusive_scan(padded) / bm; row_tok[pad_off[e] + rank] =
+    t and -1 everywhere else, the last slot included; padpos[t, j] is the
+    padded row of the assignment. An assignment to a non-local expert (EP)
+    gets padpos = rows_max - 1 and w = 0."""
+    T = logits.shape[0]
+    k, E_l = top_k, experts_local
+    dev = logits.device
+    w, idx = moe_route_select(logits, k)
+    e_loc = idx.reshape(-1) - expert_base
+    valid = (e_loc >= 0) & (e_loc < E_l)
+    w = torch.where(valid.view(T, k), w, torch.zeros_like(w))
+    # non-local assignments sort behind every local expert
+    e_key = torch.where(valid, e_loc, torch.full_like(e_loc, E_l))
+    order = torch.argsort(e_key, stable=True)
+    sorted_e = e_key[order]
+    counts = torch.bincount(e_key, minlength=E_l + 1)[:E_l]
+    padded = (counts + (bm - 1)) // bm * bm
+    pad_off = torch.zeros(E_l + 2, dtype=torch.long, device=dev)
+    pad_off[1:E_l + 1] = torch.cumsum(padded, 0)
+    rows_max = T * k + E_l * bm
+    first = torch.searchsorted(sorted_e, sorted_e, side="left")
+    rank = torch.arange(T * k, device=dev) - first
+    pos_sorted = torch.where(sorted_e < E_l, pad_off[sorted_e] + rank,
+                             torch.full_like(rank, rows_max - 1))
+    padpos = torch.empty(T * k, dtype=torch.long, device=dev)
+    padpos[order] = pos_sorted
+    row_tok = torch.full((rows_max,), -1, dtype=torch.int32, device=dev)
+    local = sorted_e < E_l
+    row_tok[pos_sorted[local]] = (order[local] // k).to(torch.int32)
+    return (w, padpos.view(T, k), row_tok,
+            (pad_off[:E_l + 1] // bm).to(torch.int32),
+            counts.to(torch.int32))
+
+
 def grouped_gemm(out, a, w, row_tok, tile_off, counts, max_tiles, gate_silu,
                  bm: int = 64):
     """Reference for csrc/grouped_gemm.hip: per-expert segments padded to the
