@@ -51,6 +51,13 @@ void sutro_attn_decode_shared(void*, const void*, const void*, const void*,
                               float, int, int, const int*, const int*, int,
                               int, float*, float*, float*, hipStream_t);
 int sutro_attn_prefix_tile_rows(int, int);
+int sutro_attn_decode_split(void*, float*, float*, float*, const void*,
+                            const void*, const void*, const int*, const int*,
+                            int, int, int, int, int, int, int, float, int,
+                            const float*, hipStream_t);
+int sutro_attn_decode_split_min_pages();
+int sutro_attn_decode_split_waves();
+int sutro_attn_decode_split_max();
 void sutro_mfma32_probe(float*, const void*, const void*, hipStream_t);
 void sutro_gemm_tn_launch(void*, const void*, const void*, const void*, int,
                           int, long, int, int, int, int, hipStream_t);
@@ -297,6 +304,77 @@ void paged_attention_decode_shared(
       tile_rows.data_ptr<int>(), (int)tile_rows.size(0),
       (int)tile_rows.size(1), part_o.data_ptr<float>(),
       part_m.data_ptr<float>(), part_l.data_ptr<float>(), cur_stream());
+}
+
+// decode rows of a batch on the split-KV kernels (attn_decode_split.hip):
+// the trailing num_decodes sequences, whose q / out rows start at flat row
+// prefill_token_count. kv_splits = S block-splits per (row, kv head); S > 1
+// passes the f32 state through ws_o [>= n, Hq, S, D], ws_m / ws_l
+// [>= n, Hq, S]; S == 1 stores directly and reads no workspace.
+void paged_attention_decode_split(
+    torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
+    torch::Tensor v_cache, torch::Tensor block_tables, torch::Tensor seq_lens,
+    double scale, int64_t num_decodes, int64_t prefill_token_count,
+    int64_t kv_splits, torch::Tensor ws_o, torch::Tensor ws_m,
+    torch::Tensor ws_l, c10::optional<torch::Tensor> sinks) {
+  CHECK_CUDA(q); CHECK_CONTIG(q); CHECK_BF16(q); CHECK_CONTIG(k_cache);
+  CHECK_CUDA(out); CHECK_CONTIG(out); CHECK_BF16(out); CHECK_CONTIG(v_cache);
+  CHECK_CUDA(block_tables); CHECK_CONTIG(block_tables);
+  CHECK_CUDA(seq_lens); CHECK_CONTIG(seq_lens);
+  TORCH_CHECK(q.dim() == 3 && out.sizes() == q.sizes(),
+              "q and out must be [T, Hq, D]");
+  const int Hq = q.size(1), D = q.size(2);
+  const int Hk = k_cache.size(1);
+  const int64_t n = num_decodes, S = kv_splits;
+  TORCH_CHECK(D == 128 || D == 64,
+              "split-KV decode supports head_dim 64/128 (got ", D, ")");
+  TORCH_CHECK(k_cache.size(2) == 32, "attention kernels require kv_block_size 32");
+  TORCH_CHECK(Hq % Hk == 0 && Hq / Hk <= 8,
+              "GQA group size must divide and be <= 8");
+  TORCH_CHECK(S >= 1 && S <= sutro_attn_decode_split_max(),
+              "kv_splits must be in [1, ", sutro_attn_decode_split_max(),
+              "] (got ", S, ")");
+  TORCH_CHECK(block_tables.scalar_type() == at::kInt &&
+              seq_lens.scalar_type() == at::kInt, "index tensors must be int32");
+  TORCH_CHECK(block_tables.dim() == 2 &&
+              block_tables.size(0) == seq_lens.numel(),
+              "block_tables must be [S, width] with one row per sequence");
+  TORCH_CHECK(n >= 0 && n <= seq_lens.numel() && prefill_token_count >= 0 &&
+              prefill_token_count + n <= q.size(0),
+              "decode rows exceed the batch");
+  TORCH_CHECK(n * Hk * S < (1L << 31), "too many blocks");
+  if (S > 1) {
+    CHECK_CUDA(ws_o); CHECK_CONTIG(ws_o); CHECK_CUDA(ws_m); CHECK_CONTIG(ws_m);
+    CHECK_CUDA(ws_l); CHECK_CONTIG(ws_l);
+    TORCH_CHECK(ws_o.scalar_type() == at::kFloat &&
+                ws_m.scalar_type() == at::kFloat &&
+                ws_l.scalar_type() == at::kFloat, "split workspace must be f32");
+    TORCH_CHECK(ws_o.numel() >= n * Hq * S * D && ws_m.numel() >= n * Hq * S &&
+                ws_l.numel() >= n * Hq * S,
+                "split workspace too small for ", n, " rows x ", S, " splits");
+  }
+  const float* sinks_p = nullptr;
+  if (sinks.has_value()) {
+    const torch::Tensor& sk = *sinks;
+    TORCH_CHECK(sk.is_cuda() && sk.device() == q.device(),
+                "sinks must be on q's device");
+    TORCH_CHECK(sk.scalar_type() == at::kFloat && sk.is_contiguous() &&
+                sk.numel() == Hq, "sinks must be contiguous f32 [Hq]");
+    sinks_p = sk.data_ptr<float>();
+  }
+  const long dec_off = prefill_token_count;
+  const int rc = sutro_attn_decode_split(
+      (u_int16_t*)out.data_ptr() + dec_off * Hq * D,
+      S > 1 ? ws_o.data_ptr<float>() : nullptr,
+      S > 1 ? ws_m.data_ptr<float>() : nullptr,
+      S > 1 ? ws_l.data_ptr<float>() : nullptr,
+      (const u_int16_t*)q.data_ptr() + dec_off * Hq * D, k_cache.data_ptr(),
+      v_cache.data_ptr(), block_tables.data_ptr<int>(),
+      seq_lens.data_ptr<int>(), (int)block_tables.size(1), (int)n, Hq, Hk, D,
+      is_fp8(k_cache) ? 1 : 0, (int)(seq_lens.numel() - n), (float)scale,
+      (int)S, sinks_p, cur_stream());
+  TORCH_CHECK(rc == 0, "split-KV decode refused Hq ", Hq, ", Hk ", Hk,
+              ", head_dim ", D, ", kv_splits ", S);
 }
 
 int64_t prefix_tile_rows(int64_t Hq, int64_t Hk) {
@@ -1170,6 +1248,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "whether the pipelined prefill kernel takes (Hq, Hk, D, tile_rows)");
   m.def("paged_attention_decode_shared", &paged_attention_decode_shared,
         "decode attention, shared-prefix tiles + per-row continuation");
+  m.def("paged_attention_decode_split", &paged_attention_decode_split,
+        "decode attention, KV range split across waves and blocks",
+        py::arg("out"), py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("block_tables"), py::arg("seq_lens"), py::arg("scale"),
+        py::arg("num_decodes"), py::arg("prefill_token_count"),
+        py::arg("kv_splits"), py::arg("ws_o"), py::arg("ws_m"),
+        py::arg("ws_l"), py::arg("sinks") = py::none());
+  m.def("decode_split_constants", []() {
+          return std::make_tuple(sutro_attn_decode_split_waves(),
+                                 sutro_attn_decode_split_min_pages(),
+                                 sutro_attn_decode_split_max());
+        }, "(waves per block, MIN_PAGES, S_MAX) of attn_decode_split.hip");
   m.def("prefix_tile_rows", &prefix_tile_rows,
         "rows per shared-prefix tile for a (Hq, Hk) head layout");
   m.def("mfma32_probe", &mfma32_probe, "MFMA fragment-layout probe");

@@ -207,8 +207,14 @@ def models():
 @click.option("--local-attention", is_flag=True, default=False,
               help="run sliding-window layers with their window and "
                    "attention sinks where the model has them (gpt-oss)")
+@click.option("--decode-kv-splits", default="off",
+              type=click.Choice(["off", "auto"]),
+              help="split-KV decode attention: split a row's KV range "
+                   "across waves and blocks where few or long rows leave "
+                   "the per-row kernel short of waves")
 def serve(host: str, port: int, device: str, moe_weight_dtype: str,
-          moe_routing: str, dense_weight_dtype: str, local_attention: bool):
+          moe_routing: str, dense_weight_dtype: str, local_attention: bool,
+          decode_kv_splits: str):
     """Serve the HTTP API (the same endpoint contract as api.sutro.sh)."""
     from .service.http_api import run_server
 
@@ -221,6 +227,8 @@ def serve(host: str, port: int, device: str, moe_weight_dtype: str,
         engine_kwargs["dense_weight_dtype"] = dense_weight_dtype
     if local_attention:
         engine_kwargs["local_attention"] = True
+    if decode_kv_splits != "off":
+        engine_kwargs["decode_kv_splits"] = decode_kv_splits
     engine_kwargs = engine_kwargs or None
     run_server(host=host, port=port, device=device,
                engine_kwargs=engine_kwargs)

@@ -53,3 +53,7 @@ class ForwardBatch:
     row_prefix_pages: Optional[torch.Tensor] = None   # [S] int32
     prefix_tile_rows: Optional[torch.Tensor] = None   # [NT, R] int32
     prefix_partials: Optional[tuple] = None
+    # split-KV decode: block-splits per (row, kv head) for the decode rows
+    # (1 = the per-row kernel) and the f32 workspace (o, m, l) they share
+    kv_splits: int = 1
+    split_workspace: Optional[tuple] = None

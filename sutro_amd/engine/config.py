@@ -113,8 +113,19 @@ class EngineConfig:
     # the two can pick different experts on tied logits. Ignored for specs
     # without experts.
     moe_routing: str = "torch"
+    # split-KV decode attention: "off" runs one wave per (row, kv head);
+    # "auto" splits a row's KV range across waves and blocks for the batch
+    # sizes ops.decode_kv_splits routes (few rows, long rows), on
+    # csrc/attn_decode_split.hip (docs/ENGINE.md, "Split-KV decode"). Layers
+    # with a window keep the per-row kernel; with prefix_decode="shared"
+    # active it stays off.
+    decode_kv_splits: str = "off"
 
     def __post_init__(self) -> None:
+        if self.decode_kv_splits not in ("off", "auto"):
+            raise ValueError(
+                f"decode_kv_splits must be 'off' or 'auto', "
+                f"got {self.decode_kv_splits!r}")
         if self.moe_routing not in ("torch", "fused"):
             raise ValueError(
                 f"moe_routing must be 'torch' or 'fused', "

@@ -218,6 +218,35 @@ class LLMEngine:
                     f"{self.spec.head_dim}, {hq}/{hk} heads, block "
                     f"{cfg.kv_block_size}); running 'per_row'")
 
+        # split-KV decode attention ("auto"): per decode batch size the rule
+        # ops.decode_kv_splits names the block-splits; off for an engine that
+        # runs shared-prefix decode (the CONT resume is not split) and for
+        # head layouts the MFMA decode route does not take
+        self.decode_split = False
+        self._split_workspace = None
+        self.decode_kv_splits_fallback: Optional[str] = None
+        if cfg.decode_kv_splits == "auto":
+            from .. import ops
+
+            hq, hk = self.local_heads()
+            if cfg.prefix_decode == "shared" and cfg.enable_prefix_caching:
+                self.decode_kv_splits_fallback = (
+                    "decode_kv_splits='auto' does not combine with "
+                    "prefix_decode='shared'; running decode_kv_splits='off'")
+            elif not ops.shared_decode_supported(self.spec.head_dim, hq, hk,
+                                                 cfg.kv_block_size):
+                self.decode_kv_splits_fallback = (
+                    f"decode_kv_splits='auto' needs head_dim 64/128, a GQA "
+                    f"group <= 8 and kv_block_size 32 (got head_dim "
+                    f"{self.spec.head_dim}, {hq}/{hk} heads, block "
+                    f"{cfg.kv_block_size}); running decode_kv_splits='off'")
+            else:
+                self.decode_split = True
+            if self.decode_kv_splits_fallback:
+                import warnings
+
+                warnings.warn(self.decode_kv_splits_fallback)
+
         self.graph_runner = None
         if (cfg.device.startswith("cuda") and not cfg.enforce_eager
                 and not self.spec.embedding):
@@ -382,6 +411,8 @@ class LLMEngine:
         prefix_kw = {}
         if self.prefix_shared and sb.num_prefills == 0 and S > 0:
             prefix_kw = self._prefix_tiles_eager(sb, block_tables, seq_lens)
+        if self.decode_split and sb.num_decodes > 0:
+            prefix_kw = self.split_kw(sb.num_decodes)
 
         dev = self.device
         return ForwardBatch(
@@ -401,6 +432,28 @@ class LLMEngine:
             prefill_token_count=prefill_token_count,
             prefill_tile_rows=tile_step,
         )
+
+    def split_kw(self, n_dec: int) -> dict:
+        """ForwardBatch fields of split-KV decode for `n_dec` decode rows:
+        S = ops.decode_kv_splits(n_dec, local Hk, widest block table), the
+        same for a graph bucket and an eager step. The one workspace is
+        sized on first use, outside any graph capture, for the largest
+        n * S(n) of any row count up to max_num_seqs (the graph runner's
+        buckets among them)."""
+        from .. import ops
+
+        hq, hk = self.local_heads()
+        bs = self.cfg.kv_block_size
+        max_pages = (self.cfg.max_model_len + bs - 1) // bs
+        s = ops.decode_kv_splits(n_dec, hk, max_pages)
+        if s <= 1 or not self.device.startswith("cuda"):
+            return dict(kv_splits=s)
+        if self._split_workspace is None:
+            slots = max(n * ops.decode_kv_splits(n, hk, max_pages)
+                        for n in range(1, self.cfg.max_num_seqs + 1))
+            self._split_workspace = ops.alloc_decode_split_workspace(
+                slots, hq, self.spec.head_dim, 1, self.device)
+        return dict(kv_splits=s, split_workspace=self._split_workspace)
 
     def _prefix_tiles_eager(self, sb: ScheduledBatch, block_tables: np.ndarray,
                             seq_lens: np.ndarray) -> dict:

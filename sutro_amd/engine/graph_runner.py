@@ -12,6 +12,8 @@ seq_len 1, so replayed kernels touch only scratch memory for them.
 
 from __future__ import annotations
 
+import contextlib
+import gc
 from typing import Dict, List, Optional
 
 import numpy as np
@@ -19,6 +21,29 @@ import torch
 
 from .batch import ForwardBatch, ScheduledBatch
 from .prefix_groups import fill_prefix_tiles, max_tiles
+
+
+@contextlib.contextmanager
+def capture_gc_guard():
+    """Keep Python's cycle collector out of a stream capture.
+
+    An engine and its graph runner reference each other, so a dropped engine
+    (a model swap, a test that built one) waits for the cycle collector, and
+    its hipGraphs with it. Destroying a hipGraph synchronises the device,
+    which is illegal while a stream captures in the global error mode: the
+    check throws inside the destructor and the process aborts. torch.cuda.graph
+    no longer collects before a capture (torch.compiler.config.
+    force_cudagraph_gc is off by default), and a capture allocates enough
+    Python objects to start a collection. So: collect now, while destroying
+    a graph is legal, and keep the collector off until the captures are done."""
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 class DecodeGraphRunner:
@@ -114,6 +139,9 @@ class DecodeGraphRunner:
         )
 
     def _prefix_fb(self, n: int) -> dict:
+        if getattr(self.engine, "decode_split", False):
+            # split-KV decode: S(n) per bucket, fixed at capture
+            return self.engine.split_kw(n)
         if not self.prefix_shared:
             return {}
         nt = max_tiles(n, self.d_tile_rows.shape[1])
@@ -121,8 +149,12 @@ class DecodeGraphRunner:
                     prefix_tile_rows=self.d_tile_rows[:nt],
                     prefix_partials=tuple(t[:n] for t in self.d_partials))
 
-    @torch.no_grad()
     def _capture_all(self) -> None:
+        with capture_gc_guard():
+            self._capture_buckets()
+
+    @torch.no_grad()
+    def _capture_buckets(self) -> None:
         eng = self.engine
         torch.cuda.synchronize()
         self._pool = torch.cuda.graph_pool_handle()

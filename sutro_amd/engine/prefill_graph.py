@@ -104,7 +104,9 @@ class PrefillGraphRunner:
             ctx = torch.cuda.graph(g, pool=pool)
         else:
             ctx = torch.cuda.graph(g)
-        with ctx:
+        from .graph_runner import capture_gc_guard
+
+        with capture_gc_guard(), ctx:
             hidden = eng.model(self._fb, eng.kv)
         self.graph = g
         self.hidden_out = hidden

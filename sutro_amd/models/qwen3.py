@@ -233,7 +233,12 @@ class Qwen3Attention(nn.Module):
                                     fb.num_decodes_tail, fb.tile_seq, fb.tile_q0,
                                     fb.prefill_token_count,
                                     tile_rows=fb.prefill_tile_rows,
-                                    window=self.window, sinks=self.sinks)
+                                    window=self.window, sinks=self.sinks,
+                                    # a windowed layer reads a few pages:
+                                    # it keeps the per-row kernel
+                                    kv_splits=1 if self.window > 0
+                                    else fb.kv_splits,
+                                    split_workspace=fb.split_workspace)
         return self.tp.all_reduce(
             _dense_linear(self.o_proj, o.view(T, self.q_size)))
 

@@ -374,8 +374,17 @@ def paged_attention(
     prefill_variant: Optional[str] = None,
     window: int = 0,
     sinks: Optional[torch.Tensor] = None,
+    kv_splits: int = 1,
+    split_workspace: Optional[tuple] = None,
 ) -> torch.Tensor:
     """Attention of new tokens vs full cached KV (causal within the new chunk).
+
+    `kv_splits` S > 1: on the GPU the decode rows run the split-KV kernels
+    (csrc/attn_decode_split.hip), S block-splits per (row, kv head), with
+    `split_workspace` from `alloc_decode_split_workspace` (allocated here when
+    None: not under graph capture). `set_decode_kv_splits` overrides S for
+    such calls. Not with a window; prefill tiles of the call are untouched,
+    and the CPU statement is the same for every S.
 
     `window` W > 0: a query at position i sees keys i - W < j <= i (0: all
     keys <= i). `sinks`: f32 [Hq], one extra softmax logit per head that adds
@@ -390,6 +399,11 @@ def paged_attention(
     tiles only) or "pipe"; None picks by the routing above: tiles of more
     than 32 rows need the pipelined kernel, 32-row tiles run it where the
     rule (or the env switch) routes this head layout to it."""
+    if kv_splits < 1:
+        raise ValueError(f"kv_splits must be >= 1, got {kv_splits}")
+    if kv_splits > 1 and window > 0:
+        raise ValueError("split-KV decode takes no window: a windowed layer "
+                         "passes kv_splits=1")
     if _use_hip(q):
         out = torch.empty_like(q)
         if tile_seq is None:
@@ -397,6 +411,18 @@ def paged_attention(
             tile_q0 = tile_seq
         if window < 0:
             raise ValueError(f"window must be >= 0, got {window}")
+        if (kv_splits > 1 and num_decodes_tail > 0
+                and _DECODE_SPLIT_FORCE != "off"):
+            # decode rows on the split kernels; the prefill tiles, if any,
+            # through the ordinary entry with no decode rows
+            _paged_attention_split(
+                out, q, k_cache, v_cache, block_tables, seq_lens, scale,
+                num_decodes_tail, prefill_token_count, sinks,
+                kv_splits if _DECODE_SPLIT_FORCE is None
+                else _DECODE_SPLIT_FORCE, split_workspace)
+            if tile_seq.numel() == 0:
+                return out
+            num_decodes_tail = 0
         if window > 0 or sinks is not None:
             _require_hip().paged_attention(
                 out, q, k_cache, v_cache, block_tables, seq_lens,
@@ -419,6 +445,109 @@ def paged_attention(
     return torch_ref.paged_attention(q, k_cache, v_cache, block_tables,
                                      seq_lens, query_start_locs, scale,
                                      window=window, sinks=sinks)
+
+
+# ---- split-KV decode (csrc/attn_decode_split.hip) ----
+# mirrors of the kernel file's constants: waves per block, the fewest pages
+# worth a wave, and the most block-splits a row takes
+DECODE_SPLIT_WAVES = 4
+DECODE_SPLIT_MIN_PAGES = 4
+DECODE_SPLIT_S_MAX = 16
+
+# The "auto" routing of EngineConfig.decode_kv_splits. The per-row kernel
+# runs n_dec * Hk waves; a decode batch is split while that count is at most
+# `wave_target`, into the `splits` entry (max waves, S) of the first step
+# that holds it, S <= `s_max`. Filled from profiles/PROFILES.md capture S1 by
+# the project's margin: a step names the S whose median beat the per-row
+# kernel's by more than twice the larger min-max spread of the two at EVERY
+# measured context (1024 .. 32768), head layout and KV dtype of the step's
+# wave count, and of those the fastest at the long contexts; wave counts
+# between two measured ones take the S of the larger. Above the target
+# (n_dec = 512 at Hk = 8, and every layout at n_dec = 2048) the split
+# kernels lost or tied and the rule returns 1. S is also capped so that the
+# longest row the caller allows (max_pages) can give every wave
+# DECODE_SPLIT_MIN_PAGES pages: below 32 pages nothing was measured.
+DECODE_SPLIT_RULE: dict = {
+    "wave_target": 512,
+    "s_max": 16,
+    "splits": ((16, 16), (64, 8), (128, 4), (512, 2)),
+}
+
+
+def _parse_decode_kv_splits(mode):
+    """None | "off" | S (int or digits, 1..S_MAX) -> None | "off" | int."""
+    if mode is None or mode == "off":
+        return mode
+    try:
+        s = int(mode)
+    except (TypeError, ValueError):
+        s = 0
+    if not 1 <= s <= DECODE_SPLIT_S_MAX:
+        raise ValueError(f"bad decode kv splits {mode!r}: expected 'off' or "
+                         f"1..{DECODE_SPLIT_S_MAX}")
+    return s
+
+
+# SUTRO_DECODE_KV_SPLITS=off keeps every call on the per-row kernel, =S runs
+# the split kernels at S block-splits wherever a caller asks for kv_splits > 1
+# (S = 1: the intra-block split alone, stored directly) (A/B and tests only);
+# unset follows the caller's kv_splits, i.e. DECODE_SPLIT_RULE.
+_DECODE_SPLIT_FORCE = _parse_decode_kv_splits(
+    os.environ.get("SUTRO_DECODE_KV_SPLITS") or None)
+
+
+def set_decode_kv_splits(mode) -> None:
+    """In-process form of SUTRO_DECODE_KV_SPLITS: "off", an S in 1..S_MAX, or
+    None to restore the measured rule."""
+    global _DECODE_SPLIT_FORCE
+    _DECODE_SPLIT_FORCE = _parse_decode_kv_splits(mode)
+
+
+def decode_kv_splits(n_dec: int, num_kv_heads: int, max_pages: int) -> int:
+    """Block-splits S for a decode batch of `n_dec` rows whose longest row
+    may reach `max_pages` KV pages; 1 = the per-row kernel. A pure function
+    of its arguments and the force switch. Under a forced S it returns
+    max(S, 2): any value > 1 routes a call to the split kernels, which then
+    run the forced S."""
+    if _DECODE_SPLIT_FORCE == "off" or n_dec < 1:
+        return 1
+    if _DECODE_SPLIT_FORCE is not None:
+        return max(_DECODE_SPLIT_FORCE, 2)
+    rule = DECODE_SPLIT_RULE
+    waves = n_dec * max(num_kv_heads, 1)
+    if waves > rule["wave_target"]:
+        return 1
+    s = next(s for top, s in rule["splits"] if waves <= top)
+    fit = max_pages // (DECODE_SPLIT_WAVES * DECODE_SPLIT_MIN_PAGES)
+    while s > max(fit, 1):
+        s //= 2
+    return min(s, rule["s_max"])
+
+
+def alloc_decode_split_workspace(n: int, num_heads: int, head_dim: int,
+                                 splits: int, device):
+    """f32 state the split kernel hands to the merge kernel: (O [n, Hq, S, D]
+    un-normalised, m [n, Hq, S], l [n, Hq, S]). Never cleared: the merge reads
+    only the slots the row's length says were written."""
+    return (torch.empty((n, num_heads, splits, head_dim), dtype=torch.float32,
+                        device=device),
+            torch.empty((n, num_heads, splits), dtype=torch.float32,
+                        device=device),
+            torch.empty((n, num_heads, splits), dtype=torch.float32,
+                        device=device))
+
+
+def _paged_attention_split(out, q, k_cache, v_cache, block_tables, seq_lens,
+                           scale, num_decodes, prefill_token_count, sinks,
+                           splits: int, workspace) -> None:
+    if splits > 1 and workspace is None:
+        workspace = alloc_decode_split_workspace(
+            num_decodes, q.shape[1], q.shape[2], splits, q.device)
+    elif splits == 1:
+        workspace = (out, out, out)   # not read
+    _require_hip().paged_attention_decode_split(
+        out, q, k_cache, v_cache, block_tables, seq_lens, scale, num_decodes,
+        prefill_token_count, splits, *workspace, sinks)
 
 
 PREFIX_CB = 4  # column blocks per wave of attn_prefix_partial_kernel

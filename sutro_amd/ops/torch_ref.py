@@ -99,6 +99,8 @@ def paged_attention(
     T, hq, d = q.shape
     nb, hk, bs, _ = k_cache.shape
     group = hq // hk
+    # computed in f32; f64 inputs (a test's high-precision reference) stay f64
+    ct = torch.float64 if q.dtype == torch.float64 else torch.float32
     out = torch.empty_like(q)
     S = seq_lens.numel()
     for s in range(S):
@@ -109,9 +111,9 @@ def paged_attention(
         L = int(seq_lens[s])
         nblk = (L + bs - 1) // bs
         blocks = block_tables[s, :nblk].long()
-        keys = k_cache[blocks].transpose(0, 1).reshape(hk, nblk * bs, d)[:, :L].float()
-        vals = v_cache[blocks].transpose(0, 1).reshape(hk, nblk * bs, d)[:, :L].float()
-        qs = q[q0:q1].float()  # [nq, hq, d]
+        keys = k_cache[blocks].transpose(0, 1).reshape(hk, nblk * bs, d)[:, :L].to(ct)
+        vals = v_cache[blocks].transpose(0, 1).reshape(hk, nblk * bs, d)[:, :L].to(ct)
+        qs = q[q0:q1].to(ct)  # [nq, hq, d]
         # head-major: [hq, nq, d]
         qs = qs.transpose(0, 1)
         kh = keys.repeat_interleave(group, dim=0)   # [hq, L, d]
@@ -126,7 +128,7 @@ def paged_attention(
         scores.masked_fill_(mask.unsqueeze(0), float("-inf"))
         if sinks is not None:
             # the sink is one more logit column; its probability is dropped
-            col = sinks.float().to(q.device).view(hq, 1, 1).expand(hq, nq, 1)
+            col = sinks.to(ct).to(q.device).view(hq, 1, 1).expand(hq, nq, 1)
             probs = torch.softmax(torch.cat([scores, col], dim=-1),
                                   dim=-1)[..., :L]
         else:
