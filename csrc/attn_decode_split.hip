@@ -45,8 +45,6 @@
 #define SPLIT_MIN_PAGES 4  // fewest pages worth a wave (ops.DECODE_SPLIT_MIN_PAGES)
 #define SPLIT_S_MAX 16     // most block-splits a row takes (ops rule: S_MAX)
 
-#define NO_PACKED_F32 __attribute__((target("no-packed-fp32-ops")))
-
 // one wave's page-walk images; the layout of the per-row kernel's MfmaSmem
 template <int D>
 struct SplitSmem {

@@ -21,6 +21,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
+typedef int i32x8 __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ float bf2f(u16 v) {
   return __uint_as_float(((u32)v) << 16);
@@ -77,6 +78,15 @@ __device__ __forceinline__ float wave_sum_f32(float v) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
 }
+
+// kernel attribute: no v_pk_*_f32. Beside MFMAs a v_pk_fma_f32 costs more
+// than the two v_fma_f32 it replaces, and plain -O3 would pack f32 folds and
+// reductions
+#if defined(__HIP_DEVICE_COMPILE__)
+#define NO_PACKED_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define NO_PACKED_F32  // the host pass does not know the feature
+#endif
 
 #define HIP_CHECK_LAUNCH()                                                 \
   do {                                                                     \

@@ -15,7 +15,7 @@
 // Serves the four per-layer decode GEMMs + lm_head at batch>=128 where
 // hipBLASLt's M=1024 algorithms leave throughput on the table (see
 // profiles/PROFILES.md); odd shapes fall back to torch.mm in python.
-#include "common.h"
+#include "lds_tile.h"
 
 typedef s16x8 bf16x8;
 
@@ -23,22 +23,13 @@ __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
-// direct HBM->LDS 16-byte copy; dst must be wave-uniform base + lane*16
-__device__ __forceinline__ void glds16(const u32* g, u32* lds) {
-  __builtin_amdgcn_global_load_lds(
-      (const __attribute__((address_space(1))) u32*)g,
-      (__attribute__((address_space(3))) u32*)lds, 16, 0, 0);
-}
-
 // LDS swizzle of a byte offset within a tile (involutions, bits >=7 fixed):
 // mode 1: the guide's st_16x32 (bit9 -> bit5), 8-way -> 4-way conflicts.
-// mode 2: row bits 1..3 XOR'd into the 16B-chunk index — a ds_read_b128
-//   quarter (16 consecutive rows, fixed k-chunk) hits all 16 bank groups:
-//   group = 8*(row&1) + (chunk ^ ((row>>1)&7)), bijective over 16 rows.
+// mode 2: swz2 of lds_tile.h, conflict-free ds_read_b128 quarters.
 template <int SWZ>
 __device__ __forceinline__ u32 swz(u32 byte) {
   if (SWZ == 1) return byte ^ (((byte >> 9) & 1u) << 5);
-  if (SWZ == 2) return byte ^ (((byte >> 8) & 7u) << 4);
+  if (SWZ == 2) return swz2(byte);
   return byte;
 }
 
@@ -61,9 +52,8 @@ __device__ __forceinline__ void stage_tile(
     const u32 lb = swz<SWZ>(b);  // pre-swizzled global source (rule 21)
     int row = (int)(lb >> 7);
     row = min(row, rows_valid - 1);  // clamp N-edge (dup loads, guarded store)
-    glds16((const u32*)((const char*)gsrc + (long)row * row_stride_b +
-                        (lb & 127u)),
-           (u32*)((char*)lds + b));
+    glds16((const char*)gsrc + (long)row * row_stride_b + (lb & 127u),
+           (char*)lds + b);
   }
 }
 
@@ -98,15 +88,8 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(
   const int wm = wave >> 2;  // wave m-row (0..1)
   const int wn = wave & 3;   // wave n-col (0..3)
 
-  // XCD-aware bijective remap (guide §5): consecutive same-XCD blocks are
-  // m-neighbours of one n-column, recovering W reuse in each XCD's L2
   int bid = blockIdx.x;
-  if (xcd_swz) {
-    const int nwg = gridDim.x;
-    const int q = nwg >> 3, r = nwg & 7;
-    const int xcd = bid & 7, seq = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + seq;
-  }
+  if (xcd_swz) bid = xcd_remap(bid, gridDim.x);
   const int m0 = (bid % (M / BM)) * BM;
   const int n0 = (bid / (M / BM)) * BN;
 

@@ -9,7 +9,7 @@
 // scale per 128x128 weight block). The statement is
 // torch_ref.fp8_block_linear; EPI 1 adds a bf16 residual in f32 before the
 // one rounding, EPI 2 is silu(g) * u on the merged [2I, K] gate_up weight.
-// The file also holds the activation quantiser that writes A_q and a_s.
+// quant_rows_fp8_block128 of quant_fp8.hip writes A_q and a_s.
 //
 // The tile, the staging and the barriers are csrc/gemm_tn_fp8_pipe.hip's,
 // unchanged: 256x256 output tile, 8 waves as 2(M)x4(N), `global_load_lds`
@@ -90,145 +90,10 @@
 // Cost of the fold, per MFMA: 4 v_fma_f32 plus 2 of the 16 factor multiplies
 // of the phase, issued while the next MFMA runs. It has not been tuned or
 // timed yet (profiles/PROFILES.md, capture B1).
-#include "common.h"
-
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-
-namespace {
-
-// e8m0 1.0 in every byte: the hardware block scale is a no-op
-constexpr int SCALE_ONE = 0x7f7f7f7f;
-
-__device__ __forceinline__ f32x4 mfma128z(i32x8 a, i32x8 b) {
-  return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
-      a, b, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0, SCALE_ONE, 0, SCALE_ONE);
-}
-
-// direct HBM->LDS 16-byte copy; lds is the wave-uniform base, lane l lands at
-// lds + l*16
-__device__ __forceinline__ void glds16(const char* g, char* lds) {
-  __builtin_amdgcn_global_load_lds(
-      (const __attribute__((address_space(1))) u32*)g,
-      (__attribute__((address_space(3))) u32*)lds, 16, 0, 0);
-}
-
-// the same for 4 bytes a lane: lane l lands at lds + l*4
-__device__ __forceinline__ void glds4(const char* g, char* lds) {
-  __builtin_amdgcn_global_load_lds(
-      (const __attribute__((address_space(1))) u32*)g,
-      (__attribute__((address_space(3))) u32*)lds, 4, 0, 0);
-}
-
-// swizzle mode 2 of gemm_tn.hip: row bits 1..3 XOR'd into the 16B chunk idx
-__device__ __forceinline__ u32 swz(u32 byte) {
-  return byte ^ (((byte >> 8) & 7u) << 4);
-}
-
-constexpr int HT = 16384;       // half-tile bytes
-constexpr int KTILE_B = 65536;  // one K-tile buffer: 4 half-tiles
-constexpr int SLOT_B0 = 0, SLOT_A0 = 1, SLOT_B1 = 2, SLOT_A1 = 3;
-
-// this thread's two staging sources of one half-tile (k = 0), rows clamped
-struct Src {
-  const char* p[2];
-};
-
-__device__ __forceinline__ Src make_src(const u8* base, long row0,
-                                        long rows_valid, long Kb, int wave,
-                                        int lane) {
-  Src s;
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const u32 b = (u32)(wave * 2 + j) * 1024u + (u32)lane * 16u;
-    const u32 lb = swz(b);  // pre-swizzled source, lane-linear LDS
-    long row = (long)(lb >> 7);
-    row = row < rows_valid ? row : rows_valid - 1;  // edge: dup rows
-    s.p[j] = (const char*)base + (row0 + row) * Kb + (lb & 127u);
-  }
-  return s;
-}
-
-__device__ __forceinline__ void stage_half(char* slot_wave, const Src& s,
-                                           long koff) {
-  glds16(s.p[0] + koff, slot_wave);
-  glds16(s.p[1] + koff, slot_wave + 1024);
-}
-
-// 32 operand bytes of one lane: two 16-byte ds_reads at the pre-swizzled
-// offsets of chunks 2q and 2q+1
-__device__ __forceinline__ i32x8 lds_frag(const char* smem, u32 off_lo,
-                                          u32 off_hi) {
-  const u32x4 lo = *(const u32x4*)(smem + off_lo);
-  const u32x4 hi = *(const u32x4*)(smem + off_hi);
-  return i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3],
-               (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
-}
-
-}  // namespace
-
-// ---- activation quantiser: bf16 [R, K] -> e4m3 [R, K] + f32 [K/128, R] ----
-// Every group of 128 consecutive K elements of a row gets its own scale, by
-// the rule of quant_rows_fp8 (csrc/grouped_gemm_fp8.hip): scale = amax / 448
-// (true f32 division; 1 for an all-zero group), code = e4m3_rne(clamp(x /
-// scale, -448, 448)) — torch_ref.quantize_rows_fp8_block128, which this
-// matches bit for bit. A group is 16 lanes of one 16-byte load each, so a
-// wave takes 4 groups and the amax is a 16-lane reduction. The scale goes to
-// out_scale[kb * lds + row] (K-block-major, row stride lds >= R).
-__global__ void __launch_bounds__(256) quant_rows_fp8_block128_kernel(
-    u8* __restrict__ out_q,         // [R, K] e4m3
-    float* __restrict__ out_scale,  // [K/128, lds]
-    const u16* __restrict__ x,      // [R, K] bf16
-    long R, int KB, long lds) {
-  const int lane = threadIdx.x & 63;
-  const long g = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 4 + (lane >> 4);
-  const bool live = g < R * KB;
-  const long off = g * 128 + (lane & 15) * 8;  // group g starts at g * 128
-  u16x8 v = u16x8{0, 0, 0, 0, 0, 0, 0, 0};
-  if (live) v = *(const u16x8*)(x + off);
-  float amax = 0.f;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(bf2f(v[e])));
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
-  if (!live) return;
-  const float scale = amax > 0.f ? amax / 448.0f : 1.0f;
-  if ((lane & 15) == 0) out_scale[(g % KB) * lds + g / KB] = scale;
-  u32 w[2];
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    float f[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      f[e] = fminf(fmaxf(bf2f(v[p * 4 + e]) / scale, -448.0f), 448.0f);
-    w[p] = (u32)f2fp8x2(f[0], f[1]) | ((u32)f2fp8x2(f[2], f[3]) << 16);
-  }
-  *(u32x2*)(out_q + off) = u32x2{w[0], w[1]};
-}
-
-// K % 128 == 0, lds >= R. Static grid, no host sync, no hipGetLastError: runs
-// inside captured decode steps.
-extern "C" void sutro_quant_rows_fp8_block128(void* out_q, float* out_scale,
-                                              const void* x, long R, long K,
-                                              long lds, hipStream_t stream) {
-  if (R == 0) return;
-  const long KB = K / 128;
-  const long groups = R * KB;
-  hipLaunchKernelGGL(quant_rows_fp8_block128_kernel,
-                     dim3((unsigned)((groups + 15) / 16)), dim3(256), 0,
-                     stream, (u8*)out_q, out_scale, (const u16*)x, R, (int)KB,
-                     lds);
-}
-
-// ---- the GEMM ----
+#include "fp8_gemm.h"
 
 // EPI: 0 = plain store, 1 = residual add, 2 = SwiGLU (out is [M, N/2])
-// no-packed-fp32-ops: beside MFMAs a v_pk_fma_f32 costs more than the two
-// v_fma_f32 it replaces, and plain -O3 would pack the fold
-#if defined(__HIP_DEVICE_COMPILE__)
-#define NO_PACKED_F32 __attribute__((target("no-packed-fp32-ops")))
-#else
-#define NO_PACKED_F32  // the host pass does not know the feature
-#endif
+// NO_PACKED_F32: the fold is scalar v_fma_f32 on purpose
 template <int EPI>
 NO_PACKED_F32 __global__ __launch_bounds__(512) void
 gemm_tn_fp8_block_pipe_kernel(
@@ -244,12 +109,7 @@ gemm_tn_fp8_block_pipe_kernel(
   const int wn = wave & 3;
 
   int bid = blockIdx.x;
-  if (xcd_swz) {
-    const int nwg = gridDim.x;
-    const int q = nwg >> 3, r = nwg & 7;
-    const int xcd = bid & 7, seq = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + seq;
-  }
+  if (xcd_swz) bid = xcd_remap(bid, gridDim.x);
   const int MT = (M + 255) >> 8;
   const int m0 = (bid % MT) * 256;
   // SwiGLU: N = 2I, a block covers 128 gate + the 128 matching up rows
@@ -280,8 +140,8 @@ gemm_tn_fp8_block_pipe_kernel(
 #pragma unroll
   for (int c = 0; c < 2; ++c) {
     const u32 kc = (u32)((lane >> 4) * 2 + c) * 16u;
-    aoff[c] = swz((u32)(wm * 64 + (lane & 15)) * 128u + kc);
-    boff[c] = swz((u32)(wn * 32 + (lane & 15)) * 128u + kc);
+    aoff[c] = swz2((u32)(wm * 64 + (lane & 15)) * 128u + kc);
+    boff[c] = swz2((u32)(wn * 32 + (lane & 15)) * 128u + kc);
   }
 
   const int KT = (int)(Kp >> 7);

@@ -5,7 +5,7 @@
 // and the dense-MLP variant out[M, I] = silu(g) * u on the merged [2I, Kp]
 // gate_up weight (gate rows 0..I-1, up rows I..2I-1, read in place), with
 // g / u the scaled gate / up products. A_q and W_q hold e4m3 codes, a_scale
-// [M] and w_scale [N] are f32 (the row quantiser of grouped_gemm_fp8.hip
+// [M] and w_scale [N] are f32 (the row quantiser of quant_fp8.hip
 // writes both), Kp is a multiple of 128 with a zero tail.
 //
 // The schedule is csrc/gemm_tn_pipe.hip's, byte for byte: 256x256 output
@@ -23,8 +23,8 @@
 // scales e8m0 1.0) per 16x16 fragment pair, K-tiles ascending into one
 // accumulator per fragment, then acc * a_scale * w_scale in the epilogue. So
 // the output is bit-identical to the grouped kernel's with one expert.
-// Operand lane map as gq_frag there: lane l supplies row l & 15 and the
-// swizzled 16-byte chunks 2q, 2q+1 of the 128-byte row, q = l >> 4.
+// Operand lane map as lds_frag_row of fp8_gemm.h: lane l supplies row l & 15
+// and the swizzled 16-byte chunks 2q, 2q+1 of the 128-byte row, q = l >> 4.
 //
 // Wave (wm, wn) owns rows wm*64..+63 of A0 and of A1 and columns wn*32..+31
 // of B0 and of B1: four 64x32 C quadrants, one per phase. In the SwiGLU
@@ -56,74 +56,7 @@
 //       8 A0 reads outstanding — before ph0's first barrier.
 // The tail keeps the counts uniform: tiles past the end are staged from the
 // last K-tile into slots whose reads are over (never read again).
-#include "common.h"
-
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-
-namespace {
-
-// e8m0 1.0 in every byte: the hardware block scale is a no-op
-constexpr int SCALE_ONE = 0x7f7f7f7f;
-
-__device__ __forceinline__ f32x4 mfma128(i32x8 a, i32x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
-      a, b, c, 0, 0, 0, SCALE_ONE, 0, SCALE_ONE);
-}
-
-// direct HBM->LDS 16-byte copy; lds is the wave-uniform base, lane l lands at
-// lds + l*16
-__device__ __forceinline__ void glds16(const char* g, char* lds) {
-  __builtin_amdgcn_global_load_lds(
-      (const __attribute__((address_space(1))) u32*)g,
-      (__attribute__((address_space(3))) u32*)lds, 16, 0, 0);
-}
-
-// swizzle mode 2 of gemm_tn.hip: row bits 1..3 XOR'd into the 16B chunk idx
-__device__ __forceinline__ u32 swz(u32 byte) {
-  return byte ^ (((byte >> 8) & 7u) << 4);
-}
-
-constexpr int HT = 16384;       // half-tile bytes
-constexpr int KTILE_B = 65536;  // one K-tile buffer: 4 half-tiles
-constexpr int SLOT_B0 = 0, SLOT_A0 = 1, SLOT_B1 = 2, SLOT_A1 = 3;
-
-// this thread's two staging sources of one half-tile (k = 0), rows clamped
-struct Src {
-  const char* p[2];
-};
-
-__device__ __forceinline__ Src make_src(const u8* base, long row0,
-                                        long rows_valid, long Kb, int wave,
-                                        int lane) {
-  Src s;
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const u32 b = (u32)(wave * 2 + j) * 1024u + (u32)lane * 16u;
-    const u32 lb = swz(b);  // pre-swizzled source, lane-linear LDS
-    long row = (long)(lb >> 7);
-    row = row < rows_valid ? row : rows_valid - 1;  // edge: dup rows
-    s.p[j] = (const char*)base + (row0 + row) * Kb + (lb & 127u);
-  }
-  return s;
-}
-
-__device__ __forceinline__ void stage_half(char* slot_wave, const Src& s,
-                                           long koff) {
-  glds16(s.p[0] + koff, slot_wave);
-  glds16(s.p[1] + koff, slot_wave + 1024);
-}
-
-// 32 operand bytes of one lane: two 16-byte ds_reads at the pre-swizzled
-// offsets of chunks 2q and 2q+1
-__device__ __forceinline__ i32x8 lds_frag(const char* smem, u32 off_lo,
-                                          u32 off_hi) {
-  const u32x4 lo = *(const u32x4*)(smem + off_lo);
-  const u32x4 hi = *(const u32x4*)(smem + off_hi);
-  return i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3],
-               (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
-}
-
-}  // namespace
+#include "fp8_gemm.h"
 
 // EPI: 0 = plain store, 1 = residual add, 2 = SwiGLU (out is [M, N/2])
 template <int EPI>
@@ -140,12 +73,7 @@ __global__ __launch_bounds__(512) void gemm_tn_fp8_pipe_kernel(
   const int wn = wave & 3;
 
   int bid = blockIdx.x;
-  if (xcd_swz) {
-    const int nwg = gridDim.x;
-    const int q = nwg >> 3, r = nwg & 7;
-    const int xcd = bid & 7, seq = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + seq;
-  }
+  if (xcd_swz) bid = xcd_remap(bid, gridDim.x);
   const int MT = (M + 255) >> 8;
   const int m0 = (bid % MT) * 256;
   // SwiGLU: N = 2I, a block covers 128 gate + the 128 matching up rows
@@ -176,8 +104,8 @@ __global__ __launch_bounds__(512) void gemm_tn_fp8_pipe_kernel(
 #pragma unroll
   for (int c = 0; c < 2; ++c) {
     const u32 kc = (u32)((lane >> 4) * 2 + c) * 16u;
-    aoff[c] = swz((u32)(wm * 64 + (lane & 15)) * 128u + kc);
-    boff[c] = swz((u32)(wn * 32 + (lane & 15)) * 128u + kc);
+    aoff[c] = swz2((u32)(wm * 64 + (lane & 15)) * 128u + kc);
+    boff[c] = swz2((u32)(wn * 32 + (lane & 15)) * 128u + kc);
   }
 
   f32x4 acc[2][2][4][2];  // [A half][B half][m frag][n frag]

@@ -19,7 +19,7 @@
 //
 // Loads. HBM -> VGPR directly, two 16-byte global loads per lane and
 // fragment: lane l supplies row l & 15 and bytes 32q .. 32q+31 of the
-// 128-byte K-tile, q = l >> 4 (gq_frag's lane map of grouped_gemm_fp8.hip
+// 128-byte K-tile, q = l >> 4 (lds_frag_row's lane map of fp8_gemm.h
 // without the LDS hop, so no swizzle). Activation fragments are loaded the
 // same way; A_q is at most 256 x Kp bytes and stays in L2. Token rows past M
 // are clamped to row M - 1 on load and never stored.
@@ -66,24 +66,14 @@
 // parameter for that A/B. Deviations from the issue's baseline: none.
 // Follow-up: a wider weight strip per block (BN = 32 / 64) to cut the
 // activation re-reads.
-#include "common.h"
-
-typedef int i32x8 __attribute__((ext_vector_type(8)));
+#include "fp8_gemm.h"
 
 namespace {
-
-// e8m0 1.0 in every byte: the hardware block scale is a no-op
-constexpr int SCALE_ONE = 0x7f7f7f7f;
 
 constexpr int DEPTH = 4;         // K-tiles a wave keeps in flight
 constexpr int RING = DEPTH + 1;  // register stages
 constexpr int BN = 16;           // weight rows per block
 constexpr int MCHUNK = 64;       // tokens per block
-
-__device__ __forceinline__ f32x4 mfma128(i32x8 a, i32x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
-      a, b, c, 0, 0, 0, SCALE_ONE, 0, SCALE_ONE);
-}
 
 // 32 operand bytes of one lane, straight from global memory, as two 16-byte
 // loads the compiler does not track: the kernel places its own counted
@@ -121,8 +111,7 @@ __device__ __forceinline__ i32x8 frag(u32x4 lo, u32x4 hi) {
 
 }  // namespace
 
-// the reduction's adds stay scalar v_add_f32
-#define NO_PACKED_F32 __attribute__((target("no-packed-fp32-ops")))
+// NO_PACKED_F32: the reduction's adds stay scalar v_add_f32
 
 // W waves, MG 16-token groups (1..4), EPI: 0 = plain store, 1 = residual add
 template <int W, int MG, int EPI>

@@ -46,7 +46,7 @@
 // RAW / WAR notes for that seam, and why the epilogue's stores cannot loosen
 // a later vmcnt(6), stand at its definition. The tile orders (tile_mn,
 // tile_mn_banded) are shared by both kernels and change no result.
-#include "common.h"
+#include "lds_tile.h"
 
 typedef s16x8 bf16x8;
 
@@ -56,32 +56,16 @@ __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
-// direct HBM->LDS 16-byte copy; lds is the wave-uniform base, lane l lands at
-// lds + l*16
-__device__ __forceinline__ void glds16(const char* g, char* lds) {
-  __builtin_amdgcn_global_load_lds(
-      (const __attribute__((address_space(1))) u32*)g,
-      (__attribute__((address_space(3))) u32*)lds, 16, 0, 0);
-}
-
 // same involutions as gemm_tn.hip (bits >= 12 fixed, so they act inside a
 // 16 KiB half-tile exactly as inside a whole tile)
 template <int SWZ>
 __device__ __forceinline__ u32 swz(u32 byte) {
   if (SWZ == 1) return byte ^ (((byte >> 9) & 1u) << 5);
-  if (SWZ == 2) return byte ^ (((byte >> 8) & 7u) << 4);
+  if (SWZ == 2) return swz2(byte);
   return byte;
 }
 
-constexpr int HT = 16384;       // half-tile bytes
-constexpr int KTILE_B = 65536;  // one K-tile buffer: 4 half-tiles
-constexpr int SLOT_B0 = 0, SLOT_A0 = 1, SLOT_B1 = 2, SLOT_A1 = 3;
-
-// this thread's two staging sources of one half-tile (k = 0), rows clamped
-struct Src {
-  const char* p[2];
-};
-
+// make_src of fp8_gemm.h with the swizzle selected (that one is mode 2 only)
 template <int SWZ>
 __device__ __forceinline__ Src make_src(const u16* base, long row0,
                                         long rows_valid, long Kb, int wave,
@@ -96,12 +80,6 @@ __device__ __forceinline__ Src make_src(const u16* base, long row0,
     s.p[j] = (const char*)base + (row0 + row) * Kb + (lb & 127u);
   }
   return s;
-}
-
-__device__ __forceinline__ void stage_half(char* slot_wave, const Src& s,
-                                           long koff) {
-  glds16(s.p[0] + koff, slot_wave);
-  glds16(s.p[1] + koff, slot_wave + 1024);
 }
 
 __device__ __forceinline__ bf16x8 lds_frag(const char* smem, u32 off) {
@@ -287,12 +265,7 @@ __global__ __launch_bounds__(512) void gemm_tn_pipe_kernel(
   const int wn = wave & 3;
 
   int bid = blockIdx.x;
-  if (xcd_swz) {
-    const int nwg = gridDim.x;
-    const int q = nwg >> 3, r = nwg & 7;
-    const int xcd = bid & 7, seq = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + seq;
-  }
+  if (xcd_swz) bid = xcd_remap(bid, gridDim.x);
   const int MT = (M + 255) >> 8;
   // SwiGLU: N = 2I, a block covers 128 gate + the 128 matching up rows
   const int I = N >> 1;

@@ -22,23 +22,12 @@
 // mode 2), mfma_f32_16x16x32_bf16, fp32 accumulate. 4 waves as 2(M)x2(N),
 // 64x64 macro-tile (expert segments average T*k/E rows — large gemm_tn
 // tiles would mostly be padding).
-#include "common.h"
+#include "lds_tile.h"
 
 typedef s16x8 bf16x8;
 
 __device__ __forceinline__ f32x4 mfma16g(bf16x8 a, bf16x8 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ void glds16g(const u32* g, u32* lds) {
-  __builtin_amdgcn_global_load_lds(
-      (const __attribute__((address_space(1))) u32*)g,
-      (__attribute__((address_space(3))) u32*)lds, 16, 0, 0);
-}
-
-// swizzle mode 2 of gemm_tn.hip: row bits 1..3 XOR'd into the 16B chunk idx
-__device__ __forceinline__ u32 gswz(u32 byte) {
-  return byte ^ (((byte >> 8) & 7u) << 4);
 }
 
 // Tile configurations (all reuse the verified gemm_tn staging recipe):
@@ -53,38 +42,10 @@ __device__ __forceinline__ u32 gswz(u32 byte) {
 // The segment padding (and tile_off table) is computed host-side with the
 // SAME BM the kernel is launched with.
 
-// Stage a ROWS x 64 bf16 tile (ROWS rows of 128B) with WAVES waves; each
-// wave issues ROWS/(8*WAVES) x 1KB chunks.
-template <int ROWS, int WAVES, bool GATHER>
-__device__ __forceinline__ void gg_stage(
-    u16* lds, const u16* gsrc, long row_stride_b, const int* row_tok,
-    int m0, int rows_valid, int wave, int lane) {
-  constexpr int CH = ROWS / (8 * WAVES);
-  static_assert(CH >= 1, "tile too small for wave count");
-#pragma unroll
-  for (int j = 0; j < CH; ++j) {
-    const int c = wave * CH + j;
-    const u32 b = (u32)c * 1024u + (u32)lane * 16u;  // lane-linear LDS byte
-    const u32 lb = gswz(b);                          // pre-swizzled source
-    int row = (int)(lb >> 7);
-    long grow;
-    if (GATHER) {
-      int r = m0 + row;
-      int tok = (row < rows_valid) ? row_tok[r] : 0;
-      if (tok < 0) tok = 0;  // padding: deterministic garbage, discarded
-      grow = (long)tok;
-    } else {
-      grow = (long)(m0 + min(row, rows_valid - 1));
-    }
-    glds16g((const u32*)((const char*)gsrc + grow * row_stride_b + (lb & 127u)),
-            (u32*)((char*)lds + b));
-  }
-}
-
 __device__ __forceinline__ const bf16x8* gg_frag(const u16* lds, int row,
                                                  int kk16) {
   u32 lb = (u32)row * 128u + (u32)kk16 * 16u;
-  return (const bf16x8*)((const char*)lds + gswz(lb));
+  return (const bf16x8*)((const char*)lds + swz2(lb));
 }
 
 // GATE_SILU=1: B has two streams (gate/up at N-offset 0 and n_cols), output
@@ -145,14 +106,16 @@ __global__ __launch_bounds__(WROWS* WCOLS * 64) void grouped_gemm_kernel(
 
   // prologue
   if (GATE_SILU)
-    gg_stage<BM, WAVES, true>(smem[0], aa, Kb, rt, m0, rows_valid, wave, lane);
+    grouped_stage<BM, WAVES, true>(smem[0], aa, Kb, rt, m0, rows_valid, wave,
+                                   lane);
   else
-    gg_stage<BM, WAVES, false>(smem[0], aa, Kb, nullptr, m0, BM, wave, lane);
-  gg_stage<BN, WAVES, false>(smem[0] + b_off, wg, Kb, nullptr, 0, BN, wave,
-                             lane);
+    grouped_stage<BM, WAVES, false>(smem[0], aa, Kb, nullptr, m0, BM, wave,
+                                    lane);
+  grouped_stage<BN, WAVES, false>(smem[0] + b_off, wg, Kb, nullptr, 0, BN,
+                                  wave, lane);
   if (GATE_SILU)
-    gg_stage<BN, WAVES, false>(smem[0] + b2_off, wu, Kb, nullptr, 0, BN, wave,
-                               lane);
+    grouped_stage<BN, WAVES, false>(smem[0] + b2_off, wu, Kb, nullptr, 0, BN,
+                                    wave, lane);
   __syncthreads();
 
   const int KT = (int)(K >> 6);
@@ -164,16 +127,16 @@ __global__ __launch_bounds__(WROWS* WCOLS * 64) void grouped_gemm_kernel(
     if (kt + 1 < KT) {
       const long ko = (long)(kt + 1) * 64;
       if (GATE_SILU)
-        gg_stage<BM, WAVES, true>(smem[p ^ 1], aa + ko, Kb, rt, m0,
-                                  rows_valid, wave, lane);
+        grouped_stage<BM, WAVES, true>(smem[p ^ 1], aa + ko, Kb, rt, m0,
+                                       rows_valid, wave, lane);
       else
-        gg_stage<BM, WAVES, false>(smem[p ^ 1], aa + ko, Kb, nullptr, m0, BM,
-                                   wave, lane);
-      gg_stage<BN, WAVES, false>(smem[p ^ 1] + b_off, wg + ko, Kb, nullptr, 0,
-                                 BN, wave, lane);
+        grouped_stage<BM, WAVES, false>(smem[p ^ 1], aa + ko, Kb, nullptr, m0,
+                                        BM, wave, lane);
+      grouped_stage<BN, WAVES, false>(smem[p ^ 1] + b_off, wg + ko, Kb,
+                                      nullptr, 0, BN, wave, lane);
       if (GATE_SILU)
-        gg_stage<BN, WAVES, false>(smem[p ^ 1] + b2_off, wu + ko, Kb, nullptr,
-                                   0, BN, wave, lane);
+        grouped_stage<BN, WAVES, false>(smem[p ^ 1] + b2_off, wu + ko, Kb,
+                                        nullptr, 0, BN, wave, lane);
     }
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {

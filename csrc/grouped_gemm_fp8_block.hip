@@ -4,7 +4,7 @@
 //
 // The contract is csrc/grouped_gemm_fp8.hip's (segments padded to the tile
 // height, static grid that exits early on the device-side tile_off table,
-// binary search for the expert, row_tok gather in stage 1, gate/up double
+// expert lookup by bisection, row_tok gather in stage 1, gate/up double
 // stream, no host sync and no error-state query: it runs inside captured
 // decode steps). The operands are the dense block kernel's
 // (csrc/gemm_tn_fp8_block_pipe.hip, torch_ref.fp8_block_linear):
@@ -49,8 +49,8 @@
 //   2. per row the amax of the 128 rounded values: over the lane's n-
 //      fragments, a 16-lane shuffle reduction, then across the 4 N-waves
 //      through LDS (the tile buffers are free after the last barrier);
-//   3. the rule of quant_rows_fp8_block128: scale = amax / 448 by true
-//      division (1 for amax == 0), code = e4m3_rne(clamp(x / scale, +-448));
+//   3. the rule of quant_rows_fp8_block128 (fp8_quant_scale and
+//      fp8_quant_clamp of fp8_gemm.h, then e4m3 round-to-nearest-even);
 //   4. the codes are collected in LDS as a plain [BM][128] byte tile and
 //      leave as full 128-byte rows in 16-byte stores to act_q [rows, I];
 //      the scales go to act_s[n0 / 128, row] (row stride ldo_s).
@@ -59,42 +59,12 @@
 // Tiles (waves as WROWS(M) x WCOLS(N)): stage 1 always 128 columns wide,
 // 128x128 and 64x128 with 8 waves as 2x4; stage 2 the per-channel kernel's
 // configurations for n_cols % 128 == 0, 128x128 (2x4) and 64x64 (2x2).
-// Operand lane map and C/D layout: see csrc/grouped_gemm_fp8.hip.
-#include "common.h"
+// Operand lane map and C/D layout: see mfma128 in fp8_gemm.h.
+#include "fp8_gemm.h"
 
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-
-namespace {
-
-// e8m0 1.0 in every byte: the hardware block scale is a no-op
-constexpr int SCALE_ONE = 0x7f7f7f7f;
-
-__device__ __forceinline__ f32x4 mfma128z(i32x8 a, i32x8 b) {
-  return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
-      a, b, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0, SCALE_ONE, 0, SCALE_ONE);
-}
-
-// direct HBM->LDS copies; lds is the wave-uniform base, lane l lands at
-// lds + l*16 (glds16) / lds + l*4 (glds4)
-__device__ __forceinline__ void glds16(const u8* g, u8* lds) {
-  __builtin_amdgcn_global_load_lds(
-      (const __attribute__((address_space(1))) u32*)g,
-      (__attribute__((address_space(3))) u32*)lds, 16, 0, 0);
-}
-
-__device__ __forceinline__ void glds4(const float* g, float* lds) {
-  __builtin_amdgcn_global_load_lds(
-      (const __attribute__((address_space(1))) u32*)g,
-      (__attribute__((address_space(3))) u32*)lds, 4, 0, 0);
-}
-
-// swizzle mode 2 of gemm_tn.hip: row bits 1..3 XOR'd into the 16B chunk idx
-__device__ __forceinline__ u32 swz(u32 byte) {
-  return byte ^ (((byte >> 8) & 7u) << 4);
-}
-
-// Stage a ROWS x 128-byte tile with WAVES waves, ROWS/(8*WAVES) x 1KB chunks
-// a wave (gq_stage of csrc/grouped_gemm_fp8.hip)
+// grouped_stage of lds_tile.h with the wave-uniform LDS base: here the wave
+// index is in a scalar register (readfirstlane), and the lane-linear address
+// the shared form passes costs a register and 8 to 17 instructions a kernel.
 template <int ROWS, int WAVES, bool GATHER>
 __device__ __forceinline__ void stage_tile(
     u8* lds, const u8* gsrc, long row_stride_b, const int* row_tok, int m0,
@@ -104,7 +74,7 @@ __device__ __forceinline__ void stage_tile(
 #pragma unroll
   for (int j = 0; j < CH; ++j) {
     const u32 cb = (u32)(wave * CH + j) * 1024u;     // wave-uniform LDS base
-    const u32 lb = swz(cb + (u32)lane * 16u);        // pre-swizzled source
+    const u32 lb = swz2(cb + (u32)lane * 16u);       // pre-swizzled source
     const int row = (int)(lb >> 7);
     long grow;
     if (GATHER) {
@@ -118,25 +88,8 @@ __device__ __forceinline__ void stage_tile(
   }
 }
 
-// 32 operand bytes of one lane: k-quarter q = lane >> 4 of a 128-byte row,
-// i.e. the swizzled 16-byte chunks 2q and 2q+1
-__device__ __forceinline__ i32x8 lds_frag(const u8* lds, int row, int q) {
-  const u32 lb = (u32)row * 128u + (u32)q * 32u;
-  const u32x4 lo = *(const u32x4*)(lds + swz(lb));
-  const u32x4 hi = *(const u32x4*)(lds + swz(lb + 16u));
-  return i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3],
-               (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
-}
-
-}  // namespace
-
-// no-packed-fp32-ops: the fold is scalar v_fma_f32 on purpose, as in the
-// dense block kernel
-#if defined(__HIP_DEVICE_COMPILE__)
-#define NO_PACKED_F32 __attribute__((target("no-packed-fp32-ops")))
-#else
-#define NO_PACKED_F32  // the host pass does not know the feature
-#endif
+// NO_PACKED_F32: the fold is scalar v_fma_f32 on purpose, as in the dense
+// block kernel
 
 // GATE_Q=1: B has two streams (gate/up at N-offset 0 and n_cols), SwiGLU and
 // the group quantiser in the epilogue, out_q / out_s written (BN == 128).
@@ -278,12 +231,12 @@ grouped_gemm_fp8_block_kernel(
     i32x8 bg[NF], bu[GATE_Q ? NF : 1];
 #pragma unroll
     for (int j = 0; j < NF; ++j) {
-      bg[j] = lds_frag(bgT, wn * WN + j * 16 + dcol, q);
-      if (GATE_Q) bu[j] = lds_frag(buT, wn * WN + j * 16 + dcol, q);
+      bg[j] = lds_frag_row(bgT, wn * WN + j * 16 + dcol, q);
+      if (GATE_Q) bu[j] = lds_frag_row(buT, wn * WN + j * 16 + dcol, q);
     }
 #pragma unroll
     for (int i = 0; i < MF; ++i) {
-      const i32x8 af = lds_frag(aT, wm * WM + i * 16 + dcol, q);
+      const i32x8 af = lds_frag_row(aT, wm * WM + i * 16 + dcol, q);
       // one f32 product per (row, weight block) as the factor
       float fg[4], fu[4];
 #pragma unroll
@@ -363,15 +316,13 @@ grouped_gemm_fp8_block_kernel(
       const int row = wm * WM + i * 16 + drow + r;
       const f32x4 a4 = *(const f32x4*)&red[row * WCOLS];
       const float amax = fmaxf(fmaxf(a4[0], a4[1]), fmaxf(a4[2], a4[3]));
-      const float scale = amax > 0.f ? amax / 448.0f : 1.0f;
+      const float scale = fp8_quant_scale(amax);
       if (wn == 0 && dcol == 0)
         out_s[(long)(n0 >> 7) * ldo_s + seg0 + m0 + row] = scale;
 #pragma unroll
       for (int j = 0; j < NF; j += 2) {
-        const float f0 =
-            fminf(fmaxf(x[i][j][r] / scale, -448.0f), 448.0f);
-        const float f1 =
-            fminf(fmaxf(x[i][j + 1][r] / scale, -448.0f), 448.0f);
+        const float f0 = fp8_quant_clamp(x[i][j][r], scale);
+        const float f1 = fp8_quant_clamp(x[i][j + 1][r], scale);
         const u16 c2 = f2fp8x2(f0, f1);
         code[row * 128 + wn * WN + j * 16 + dcol] = (u8)(c2 & 0xff);
         code[row * 128 + wn * WN + (j + 1) * 16 + dcol] = (u8)(c2 >> 8);

@@ -49,7 +49,7 @@
 // the tile's global_load_lds so that the barrier that retires the staging
 // retires the scales with it.
 //
-// LDS: the A tile is staged as in the fp8 kernel (128-byte rows, qswz); a
+// LDS: the A tile is staged as in the fp8 kernel (128-byte rows, swz2); a
 // lane reads the 16-byte chunks q and 4 + q of its row. A K-tile of W is 64
 // bytes per row; one wave's 1 KiB global_load_lds piece covers 16 rows, and a
 // lane reads one 16-byte chunk (row l & 15, chunk q). ds_read_b128 serves
@@ -57,32 +57,9 @@
 // of row r is stored at chunk c ^ g((r >> 2) & 3) with g = {0, 2, 3, 1},
 // which makes every 16-lane group hit 16 distinct 16-byte bank groups.
 // tools/sim_grouped_gemm_mxfp4.py proves the staging / read bijection and the
-// conflict-freeness of the W and the A reads; the row-bit XOR of qswz would
+// conflict-freeness of the W and the A reads; the row-bit XOR of swz2 would
 // put rows 0, 2, 4, ... of W on the same banks.
-#include "common.h"
-
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-
-// e8m0 1.0 in every byte: the A-side hardware block scale is a no-op
-#define MX_SCALE_ONE 0x7f7f7f7f
-
-// A e4m3 (cbsz 0) x B e2m1 (blgp 4); opsel 0 on both scale registers
-__device__ __forceinline__ f32x4 mfma128x(i32x8 a, i32x8 b, f32x4 c,
-                                          int b_scale) {
-  return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
-      a, b, c, 0, 4, 0, MX_SCALE_ONE, 0, b_scale);
-}
-
-__device__ __forceinline__ void glds16x(const u32* g, u32* lds) {
-  __builtin_amdgcn_global_load_lds(
-      (const __attribute__((address_space(1))) u32*)g,
-      (__attribute__((address_space(3))) u32*)lds, 16, 0, 0);
-}
-
-// A tile, 128-byte rows: row bits 1..3 XOR'd into the 16B chunk index
-__device__ __forceinline__ u32 aswz(u32 byte) {
-  return byte ^ (((byte >> 8) & 7u) << 4);
-}
+#include "fp8_gemm.h"
 
 // W tile, 64-byte rows: chunk ^= g(row >> 2), g = {0, 2, 3, 1} packed in 0x78
 __device__ __forceinline__ u32 wswz(u32 byte) {
@@ -162,34 +139,6 @@ extern "C" void sutro_quant_weight_mxfp4(void* out_q, void* out_scale,
 
 // ---- grouped GEMM ----
 
-// Stage a ROWS x 128-byte A tile with WAVES waves (gq_stage of the fp8
-// kernel): each wave issues ROWS/(8*WAVES) x 1KB pieces.
-template <int ROWS, int WAVES, bool GATHER>
-__device__ __forceinline__ void gx_stage_a(
-    u8* lds, const u8* gsrc, long row_stride_b, const int* row_tok,
-    int m0, int rows_valid, int wave, int lane) {
-  constexpr int CH = ROWS / (8 * WAVES);
-  static_assert(CH >= 1, "tile too small for wave count");
-#pragma unroll
-  for (int j = 0; j < CH; ++j) {
-    const int c = wave * CH + j;
-    const u32 b = (u32)c * 1024u + (u32)lane * 16u;  // lane-linear LDS byte
-    const u32 lb = aswz(b);                          // pre-swizzled source
-    int row = (int)(lb >> 7);
-    long grow;
-    if (GATHER) {
-      int r = m0 + row;
-      int tok = (row < rows_valid) ? row_tok[r] : 0;
-      if (tok < 0) tok = 0;  // padding: deterministic garbage, discarded
-      grow = (long)tok;
-    } else {
-      grow = (long)(m0 + min(row, rows_valid - 1));
-    }
-    glds16x((const u32*)(gsrc + grow * row_stride_b + (lb & 127u)),
-            (u32*)(lds + b));
-  }
-}
-
 // Stage the W tile: NB streams of BN rows x 64 bytes, contiguous in LDS
 // (stream 1 = the up rows, n_cols further down in global). A 1KB piece is 16
 // rows; pieces are dealt round-robin to the waves (a wave-uniform branch
@@ -208,8 +157,7 @@ __device__ __forceinline__ void gx_stage_w(
     const u32 lb = wswz(b);                          // pre-swizzled source
     const int row = (int)(lb >> 6);
     const long grow = row < BN ? row : n_cols + row - BN;
-    glds16x((const u32*)(gsrc + grow * row_stride_b + (lb & 63u)),
-            (u32*)(lds + b));
+    glds16(gsrc + grow * row_stride_b + (lb & 63u), lds + b);
   }
 }
 
@@ -217,8 +165,8 @@ __device__ __forceinline__ void gx_stage_w(
 // k = 16q .. 16q+15 and 64+16q .. 64+16q+15 (16-byte chunks q and 4 + q)
 __device__ __forceinline__ i32x8 gx_frag_a(const u8* lds, int row, int q) {
   const u32 lb = (u32)row * 128u + (u32)q * 16u;
-  const u32x4 lo = *(const u32x4*)(lds + aswz(lb));
-  const u32x4 hi = *(const u32x4*)(lds + aswz(lb + 64u));
+  const u32x4 lo = *(const u32x4*)(lds + swz2(lb));
+  const u32x4 hi = *(const u32x4*)(lds + swz2(lb + 64u));
   return i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3],
                (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
 }
@@ -301,10 +249,11 @@ __global__ __launch_bounds__(WROWS* WCOLS * 64) void grouped_gemm_mxfp4_kernel(
 
   // prologue
   if (GATE_SILU)
-    gx_stage_a<BM, WAVES, true>(smem[0], aa, Kp, rt, m0, rows_valid, wave,
-                                lane);
+    grouped_stage<BM, WAVES, true>(smem[0], aa, Kp, rt, m0, rows_valid, wave,
+                                   lane);
   else
-    gx_stage_a<BM, WAVES, false>(smem[0], aa, Kp, nullptr, m0, BM, wave, lane);
+    grouped_stage<BM, WAVES, false>(smem[0], aa, Kp, nullptr, m0, BM, wave,
+                                    lane);
   gx_stage_w<BN, NB, WAVES>(smem[0] + b_off, wg, wrow_b, n_cols, wave, lane);
 #pragma unroll
   for (int j = 0; j < NF; ++j) {
@@ -322,11 +271,11 @@ __global__ __launch_bounds__(WROWS* WCOLS * 64) void grouped_gemm_mxfp4_kernel(
     if (kt + 1 < KT) {
       const long ko = (long)(kt + 1) * 128;
       if (GATE_SILU)
-        gx_stage_a<BM, WAVES, true>(smem[p ^ 1], aa + ko, Kp, rt, m0,
-                                    rows_valid, wave, lane);
+        grouped_stage<BM, WAVES, true>(smem[p ^ 1], aa + ko, Kp, rt, m0,
+                                       rows_valid, wave, lane);
       else
-        gx_stage_a<BM, WAVES, false>(smem[p ^ 1], aa + ko, Kp, nullptr, m0,
-                                     BM, wave, lane);
+        grouped_stage<BM, WAVES, false>(smem[p ^ 1], aa + ko, Kp, nullptr, m0,
+                                        BM, wave, lane);
       gx_stage_w<BN, NB, WAVES>(smem[p ^ 1] + b_off, wg + (ko >> 1), wrow_b,
                                 n_cols, wave, lane);
       // next tile's scales, behind the staging: first used after the barrier

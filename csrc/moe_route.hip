@@ -22,8 +22,6 @@
 // A block owns RT_TOK consecutive tokens in both select and scatter.
 #include "common.h"
 
-#define NO_PACKED_F32 __attribute__((target("no-packed-fp32-ops")))
-
 constexpr int RT_THREADS = 256;
 constexpr int RT_TOK = 128;       // tokens per block
 constexpr int RT_MAX_E = 128;
