@@ -95,6 +95,8 @@ void sutro_quant_weight_mxfp4(void*, void*, const void*, long, int, int,
 void sutro_grouped_gemm_mxfp4(void*, const void*, const float*, const void*,
                               const void*, const int*, const int*, const int*,
                               int, int, int, long, int, int, hipStream_t);
+void sutro_rmsnorm_quant_fp8(void*, float*, void*, const void*, const void*,
+                             float, long, int, int, long, int, hipStream_t);
 void sutro_quant_rows_fp8_block128(void*, float*, const void*, long, long,
                                    long, hipStream_t);
 int sutro_gemm_tn_fp8_block_pipe_launch(void*, const void*, const float*,
@@ -623,6 +625,41 @@ std::vector<torch::Tensor> quant_rows_fp8_block128(torch::Tensor x) {
   auto s = torch::empty({K / 128, R}, x.options().dtype(at::kFloat));
   sutro_quant_rows_fp8_block128(q.data_ptr(), s.data_ptr<float>(),
                                 x.data_ptr(), R, K, R, cur_stream());
+  return {q, s};
+}
+
+// RMSNorm of x [R, C] (after residual += x when a residual is given) straight
+// to e4m3 codes and f32 scales, bit-equal to fused_add_rmsnorm / rmsnorm
+// followed by the quantiser (csrc/rmsnorm_quant_fp8.hip). mode 0: codes
+// [R, Kp] (Kp = C rounded up to 128, zero tail) + scales [R], C % 8 == 0;
+// mode 1: codes [R, C] + scales [C/128, R], C % 128 == 0.
+std::vector<torch::Tensor> rmsnorm_quant_fp8(
+    torch::Tensor x, c10::optional<torch::Tensor> residual, torch::Tensor w,
+    double eps, int64_t mode) {
+  CHECK_CUDA(x); CHECK_CONTIG(x); CHECK_BF16(x);
+  CHECK_CUDA(w); CHECK_CONTIG(w); CHECK_BF16(w);
+  TORCH_CHECK(x.dim() == 2, "x must be 2-d");
+  TORCH_CHECK(mode == 0 || mode == 1, "mode 0 (rows) or 1 (block128)");
+  const long R = x.size(0), C = x.size(1);
+  TORCH_CHECK(C >= 8 && C % 8 == 0 && C <= 16384, "unsupported row size ", C);
+  TORCH_CHECK(mode == 0 || C % 128 == 0,
+              "block128 needs C a multiple of 128 (C=", C, ")");
+  TORCH_CHECK(w.numel() == C, "weight must have C elements");
+  TORCH_CHECK(R < (1L << 31), "too many rows");
+  void* rp = nullptr;
+  if (residual.has_value()) {
+    CHECK_CUDA(*residual); CHECK_CONTIG(*residual); CHECK_BF16(*residual);
+    TORCH_CHECK(residual->dim() == 2 && residual->size(0) == R
+                && residual->size(1) == C, "residual shape");
+    rp = residual->data_ptr();
+  }
+  const long Kp = mode == 1 ? C : (C + 127) / 128 * 128;
+  auto q = torch::empty({R, Kp}, x.options().dtype(at::kFloat8_e4m3fn));
+  auto s = mode == 1 ? torch::empty({C / 128, R}, x.options().dtype(at::kFloat))
+                     : torch::empty({R}, x.options().dtype(at::kFloat));
+  sutro_rmsnorm_quant_fp8(q.data_ptr(), s.data_ptr<float>(), rp, x.data_ptr(),
+                          w.data_ptr(), (float)eps, R, (int)C, (int)Kp, R,
+                          (int)mode, cur_stream());
   return {q, s};
 }
 
@@ -1317,6 +1354,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("quant_rows_fp8_block128", &quant_rows_fp8_block128,
         "bf16 rows -> e4m3 codes + f32 scales per group of 128 K elements",
         py::arg("x"));
+  m.def("rmsnorm_quant_fp8", &rmsnorm_quant_fp8,
+        "(residual += x;) rmsnorm -> e4m3 codes + f32 scales, one kernel",
+        py::arg("x"), py::arg("residual"), py::arg("w"), py::arg("eps"),
+        py::arg("mode"));
   m.def("gemm_fp8_block_pipelined", &gemm_fp8_block_pipelined,
         "e4m3 TN GEMM with 128x128 weight and 1x128 activation scales",
         py::arg("a_q"), py::arg("a_s"), py::arg("w_q"), py::arg("w_s"),

@@ -28,6 +28,7 @@ SOURCES = [
     "csrc/gemm_tn_fp8_skinny.hip",
     "csrc/gemm_tn_fp8_block_pipe.hip",
     "csrc/quant_fp8.hip",
+    "csrc/rmsnorm_quant_fp8.hip",
     "csrc/sampler.hip",
     "csrc/grouped_gemm.hip",
     "csrc/grouped_gemm_fp8.hip",

@@ -204,6 +204,12 @@ def models():
                    "fp8_e4m3 halves them and runs them W8A8, fp8_block128 "
                    "does so with the 128x128 block scales of the published "
                    "FP8 checkpoints)")
+@click.option("--dense-act-quant", default="separate",
+              type=click.Choice(["separate", "fused"]),
+              help="where the FP8 dense projections' activations are "
+                   "quantised: in a pass of their own, or inside the "
+                   "preceding RMSNorm kernel (same results; needs an FP8 "
+                   "--dense-weight-dtype)")
 @click.option("--local-attention", is_flag=True, default=False,
               help="run sliding-window layers with their window and "
                    "attention sinks where the model has them (gpt-oss)")
@@ -213,8 +219,8 @@ def models():
                    "across waves and blocks where few or long rows leave "
                    "the per-row kernel short of waves")
 def serve(host: str, port: int, device: str, moe_weight_dtype: str,
-          moe_routing: str, dense_weight_dtype: str, local_attention: bool,
-          decode_kv_splits: str):
+          moe_routing: str, dense_weight_dtype: str, dense_act_quant: str,
+          local_attention: bool, decode_kv_splits: str):
     """Serve the HTTP API (the same endpoint contract as api.sutro.sh)."""
     from .service.http_api import run_server
 
@@ -225,6 +231,8 @@ def serve(host: str, port: int, device: str, moe_weight_dtype: str,
         engine_kwargs["moe_routing"] = moe_routing
     if dense_weight_dtype != "bf16":
         engine_kwargs["dense_weight_dtype"] = dense_weight_dtype
+    if dense_act_quant != "separate":
+        engine_kwargs["dense_act_quant"] = dense_act_quant
     if local_attention:
         engine_kwargs["local_attention"] = True
     if decode_kv_splits != "off":

@@ -86,6 +86,14 @@ class EngineConfig:
     # csrc/gemm_tn_fp8_block_pipe.hip. Projections that arrive unquantised
     # are quantised after load; ones that are not whole blocks stay bf16.
     dense_weight_dtype: str = "bf16"
+    # where the activations of the FP8 dense projections are quantised:
+    # "separate" runs the quantiser as its own pass in front of each GEMM;
+    # "fused" quantises inside the norm whose only consumer is an FP8
+    # projection (input_layernorm -> qkv_proj, post_attention_layernorm ->
+    # gate_up_proj of a dense MLP) on csrc/rmsnorm_quant_fp8.hip, which writes
+    # codes and scales and no bf16 rows (docs/ENGINE.md, "Fused activation
+    # quantisation"). Same bits either way. Needs an FP8 dense_weight_dtype.
+    dense_act_quant: str = "separate"
     # block-hash prefix cache: full blocks of computed prompt tokens are
     # indexed by (parent block, token ids) and shared between rows by
     # reference count, so a job's common system prompt is prefilled and held
@@ -160,6 +168,16 @@ class EngineConfig:
             raise ValueError(
                 f"dense_weight_dtype must be 'bf16', 'fp8_e4m3' or "
                 f"'fp8_block128', got {self.dense_weight_dtype!r}")
+        if self.dense_act_quant not in ("separate", "fused"):
+            raise ValueError(
+                f"dense_act_quant must be 'separate' or 'fused', "
+                f"got {self.dense_act_quant!r}")
+        if self.dense_act_quant == "fused" and self.dense_weight_dtype == "bf16":
+            raise ValueError(
+                "dense_act_quant='fused' quantises activations for the FP8 "
+                "dense projections; with dense_weight_dtype='bf16' there are "
+                "none (set dense_weight_dtype to 'fp8_e4m3' or "
+                "'fp8_block128')")
         if self.device == "cpu":
             self.dtype = torch.float32
         if self.max_model_len > self.spec.max_context:

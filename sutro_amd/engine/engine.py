@@ -88,7 +88,8 @@ class LLMEngine:
                 model = Qwen3Model(self.spec, cfg.dtype, cfg.max_model_len,
                                    self.tp, moe_ep=cfg.moe_ep,
                                    local_attention=cfg.local_attention,
-                                   moe_routing=cfg.moe_routing)
+                                   moe_routing=cfg.moe_routing,
+                                   dense_act_quant=cfg.dense_act_quant)
             if cfg.weights_path:
                 from ..models.loader import load_weights
 

@@ -119,15 +119,32 @@ def _quantize_linear_fp8_block128(lin: nn.Linear) -> None:
     install_linear_fp8_block128(lin, codes, scale_inv)
 
 
-def _dense_linear(lin: nn.Linear, x: torch.Tensor) -> torch.Tensor:
+def _dense_linear(lin: nn.Linear, x, out_dtype=None) -> torch.Tensor:
     """lin(x), through the block-scaled kernel when lin carries
     `weight_scale_inv`, through the W8A8 kernel when it was quantised per
-    channel."""
+    channel. For a quantised lin, x may be the pair (codes, scales) of
+    ops.rmsnorm_quant_fp8 in lin's format; out_dtype is then the result's
+    dtype on CPU."""
     if getattr(lin, "weight_scale_inv", None) is not None:
-        return ops.linear_fp8_block128(x, lin.weight, lin.weight_scale_inv)
+        return ops.linear_fp8_block128(x, lin.weight, lin.weight_scale_inv,
+                                       out_dtype=out_dtype)
     if lin.weight.dtype == torch.float8_e4m3fn:
-        return ops.linear_fp8(x, lin.weight, lin.weight_scale)
+        return ops.linear_fp8(x, lin.weight, lin.weight_scale,
+                              out_dtype=out_dtype)
     return lin(x)
+
+
+def _fused_quant_mode(lin: nn.Linear, width: int) -> Optional[str]:
+    """The ops.rmsnorm_quant_fp8 format that feeds lin ("block128" with
+    `weight_scale_inv`, "rows" when quantised per channel), or None when lin
+    is not quantised or the kernel does not take rows of `width`."""
+    if getattr(lin, "weight_scale_inv", None) is not None:
+        mode = "block128"
+    elif lin.weight.dtype == torch.float8_e4m3fn:
+        mode = "rows"
+    else:
+        return None
+    return mode if ops.rmsnorm_quant_fp8_supported(width, mode) else None
 
 
 class RMSNorm(nn.Module):
@@ -147,6 +164,7 @@ class Qwen3Attention(nn.Module):
         super().__init__()
         tp = tp or TPContext()
         self.tp = tp
+        self.dtype = dtype
         assert spec.num_heads % tp.size == 0, "num_heads must divide tp_size"
         assert spec.num_kv_heads % tp.size == 0 or tp.size == 1, \
             "num_kv_heads must divide tp_size"
@@ -206,10 +224,12 @@ class Qwen3Attention(nn.Module):
             if ops.linear_fp8_block128_qualifies(*lin.weight.shape):
                 _quantize_linear_fp8_block128(lin)
 
-    def forward(self, x: torch.Tensor, fb: ForwardBatch, kv: PagedKVCache,
+    def forward(self, x, fb: ForwardBatch, kv: PagedKVCache,
                 cos_sin: torch.Tensor) -> torch.Tensor:
-        T = x.shape[0]
-        qkv = _dense_linear(self.qkv_proj, x)
+        """x: the normalised rows [T, hidden], or their quantised pair in
+        qkv_proj's format (Qwen3Block with dense_act_quant="fused")."""
+        T = (x[0] if isinstance(x, tuple) else x).shape[0]
+        qkv = _dense_linear(self.qkv_proj, x, self.dtype)
         q = ops.fused_qkv_prep(
             qkv, self.num_heads, self.num_kv_heads, self.head_dim,
             fb.positions, fb.slot_mapping,
@@ -249,6 +269,7 @@ class Qwen3MLP(nn.Module):
         super().__init__()
         tp = tp or TPContext()
         self.tp = tp
+        self.dtype = dtype
         assert intermediate % tp.size == 0
         inter_l = intermediate // tp.size
         self.gate_up_proj = nn.Linear(hidden, 2 * inter_l, bias=False, dtype=dtype)
@@ -287,13 +308,17 @@ class Qwen3MLP(nn.Module):
         if ops.linear_fp8_block128_qualifies(*self.down_proj.weight.shape):
             _quantize_linear_fp8_block128(self.down_proj)
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x) -> torch.Tensor:
+        """x: the normalised rows [T, hidden], or their quantised pair in
+        gate_up_proj's format (Qwen3Block with dense_act_quant="fused")."""
         gu = self.gate_up_proj
         if getattr(gu, "weight_scale_inv", None) is not None:
             act = ops.gate_up_silu_fp8_block128(x, gu.weight,
-                                                gu.weight_scale_inv)
+                                                gu.weight_scale_inv,
+                                                out_dtype=self.dtype)
         elif gu.weight.dtype == torch.float8_e4m3fn:
-            act = ops.gate_up_silu_fp8(x, gu.weight, gu.weight_scale)
+            act = ops.gate_up_silu_fp8(x, gu.weight, gu.weight_scale,
+                                       out_dtype=self.dtype)
         else:
             act = ops.gate_up_silu(x, gu.weight)
         return self.tp.all_reduce(_dense_linear(self.down_proj, act))
@@ -999,8 +1024,15 @@ class Qwen3MoE(nn.Module):
 class Qwen3Block(nn.Module):
     def __init__(self, spec: ModelSpec, dtype: torch.dtype, layer_idx: int,
                  tp: Optional[TPContext] = None, moe_ep: bool = False,
-                 local_attention: bool = False, moe_routing: str = "torch"):
+                 local_attention: bool = False, moe_routing: str = "torch",
+                 dense_act_quant: str = "separate"):
+        """dense_act_quant (EngineConfig.dense_act_quant): "fused" runs each
+        of the two norms on ops.rmsnorm_quant_fp8 when its only consumer
+        (qkv_proj; gate_up_proj of a dense MLP) is an FP8 projection, and
+        hands that projection codes and scales instead of bf16 rows. Same
+        bits as "separate"."""
         super().__init__()
+        self.dense_act_quant = dense_act_quant
         self.input_layernorm = RMSNorm(spec.hidden_size, spec.rms_eps, dtype)
         self.self_attn = Qwen3Attention(spec, dtype, layer_idx, tp,
                                         local_attention)
@@ -1011,7 +1043,33 @@ class Qwen3Block(nn.Module):
         else:
             self.mlp = Qwen3MLP(spec.hidden_size, spec.intermediate_size, dtype, tp)
 
+    def _norm_fused(self, norm: RMSNorm, consumer: Optional[nn.Linear], x,
+                    residual):
+        """(residual += x;) norm(residual) for `consumer`, the projection
+        that alone reads the result: its quantised pair when consumer is an
+        FP8 projection, bf16 rows otherwise. Returns (rows or pair,
+        residual)."""
+        mode = (None if consumer is None
+                else _fused_quant_mode(consumer, norm.weight.numel()))
+        if mode is not None:
+            x_q, x_s, residual = ops.rmsnorm_quant_fp8(
+                x, residual, norm.weight, norm.eps, mode)
+            return (x_q, x_s), residual
+        if residual is None:
+            return norm(x), x
+        return ops.fused_add_rmsnorm(x, residual, norm.weight, norm.eps)
+
     def forward(self, x, residual, fb: ForwardBatch, kv, cos_sin):
+        if self.dense_act_quant == "fused":
+            x, residual = self._norm_fused(
+                self.input_layernorm, self.self_attn.qkv_proj, x, residual)
+            x = self.self_attn(x, fb, kv, cos_sin)
+            # an MoE mlp's router reads the bf16 rows: no single consumer
+            mlp_in = (self.mlp.gate_up_proj if isinstance(self.mlp, Qwen3MLP)
+                      else None)
+            x, residual = self._norm_fused(self.post_attention_layernorm,
+                                           mlp_in, x, residual)
+            return self.mlp(x), residual
         if residual is None:
             residual = x
             x = self.input_layernorm(x)
@@ -1033,7 +1091,8 @@ class Qwen3Model(nn.Module):
 
     def __init__(self, spec: ModelSpec, dtype: torch.dtype, max_len: int,
                  tp: Optional[TPContext] = None, moe_ep: bool = False,
-                 local_attention: bool = False, moe_routing: str = "torch"):
+                 local_attention: bool = False, moe_routing: str = "torch",
+                 dense_act_quant: str = "separate"):
         super().__init__()
         self.spec = spec
         self.tp = tp or TPContext()
@@ -1043,7 +1102,7 @@ class Qwen3Model(nn.Module):
         self.embed_tokens = nn.Embedding(spec.vocab_size, spec.hidden_size, dtype=dtype)
         self.layers = nn.ModuleList(
             [Qwen3Block(spec, dtype, i, self.tp, moe_ep, self.local_attention,
-                        moe_routing)
+                        moe_routing, dense_act_quant)
              for i in range(spec.num_layers)]
         )
         self.norm = RMSNorm(spec.hidden_size, spec.rms_eps, dtype)

@@ -762,34 +762,45 @@ def linear_fp8_skinny_routed(n: int, kp: int, m: int) -> bool:
     return m <= FP8_SKINNY_RULE.get((n, kp), 0)
 
 
-def linear_fp8(x, w_q, w_scale, residual=None):
+def _is_cuda_act(x) -> bool:
+    """_use_hip for a projection's activation: a tensor or an
+    already-quantised pair (x_q, x_s)."""
+    return _use_hip(x[0] if isinstance(x, tuple) else x)
+
+
+def linear_fp8(x, w_q, w_scale, residual=None, out_dtype=None):
     """Dense W8A8 projection: x [T, K] (bf16 on GPU) through w_q [N, Kp] e4m3
     with f32 per-output-channel scales w_scale [N]; returns [T, N] in x's
     dtype, optionally + residual (added in f32 before the one rounding).
     Arithmetic: torch_ref.linear_fp8. On GPU the row quantiser runs as its
     own pass, then csrc/gemm_tn_fp8_pipe.hip, or csrc/gemm_tn_fp8_skinny.hip
     where `linear_fp8_skinny_routed` says so; no host sync, every tensor from
-    the caching allocator."""
-    if _use_hip(x):
+    the caching allocator. x may also be the already-quantised pair (x_q
+    [T, Kp], x_s [T]) of `rmsnorm_quant_fp8`: the quantiser pass is skipped
+    and the result is bf16 (on CPU: `out_dtype`)."""
+    if _is_cuda_act(x):
         C = _require_hip()
         # fresh caching-allocator tensors: safe under hipGraph capture
-        x_q, x_s = torch_ref.quantize_act_fp8(x, quantize_rows_fp8)
-        if linear_fp8_skinny_routed(w_q.shape[0], w_q.shape[1], x.shape[0]):
+        x_q, x_s = (x if isinstance(x, tuple)
+                    else torch_ref.quantize_act_fp8(x, quantize_rows_fp8))
+        if linear_fp8_skinny_routed(w_q.shape[0], w_q.shape[1], x_q.shape[0]):
             return C.gemm_fp8_skinny(x_q, x_s, w_q, w_scale, residual)
         return C.gemm_fp8_pipelined(x_q, x_s, w_q, w_scale, residual)
-    return torch_ref.linear_fp8(x, w_q, w_scale, residual)
+    return torch_ref.linear_fp8(x, w_q, w_scale, residual, out_dtype)
 
 
-def gate_up_silu_fp8(x, w_q, w_scale):
+def gate_up_silu_fp8(x, w_q, w_scale, out_dtype=None):
     """SwiGLU of the merged W8A8 gate_up projection (w_q [2I, Kp], gate rows
     first): one kernel, f32 SwiGLU on the scaled products, one rounding.
-    Arithmetic: torch_ref.gate_up_silu_fp8."""
-    if _use_hip(x):
+    Arithmetic: torch_ref.gate_up_silu_fp8. x: a tensor or an
+    already-quantised pair, as in `linear_fp8`."""
+    if _is_cuda_act(x):
         C = _require_hip()
         # fresh caching-allocator tensors: safe under hipGraph capture
-        x_q, x_s = torch_ref.quantize_act_fp8(x, quantize_rows_fp8)
+        x_q, x_s = (x if isinstance(x, tuple)
+                    else torch_ref.quantize_act_fp8(x, quantize_rows_fp8))
         return C.gemm_fp8_gate_up_silu(x_q, x_s, w_q, w_scale)
-    return torch_ref.gate_up_silu_fp8(x, w_q, w_scale)
+    return torch_ref.gate_up_silu_fp8(x, w_q, w_scale, out_dtype)
 
 
 def linear_fp8_block128_qualifies(n: int, k: int) -> bool:
@@ -815,7 +826,7 @@ def quantize_rows_fp8_block128(x):
     return torch_ref.quantize_rows_fp8_block128(x)
 
 
-def linear_fp8_block128(x, w_q, w_s, residual=None):
+def linear_fp8_block128(x, w_q, w_s, residual=None, out_dtype=None):
     """Block-scaled dense projection: x [T, K] (bf16 on GPU) through w_q
     [N, K] e4m3 with one f32 scale per 128x128 block, w_s [N/128, K/128]
     (`weight`, `weight_scale_inv` of the published block-FP8 checkpoints);
@@ -823,25 +834,56 @@ def linear_fp8_block128(x, w_q, w_s, residual=None):
     the one rounding). Arithmetic: torch_ref.linear_fp8_block128. On GPU the
     group quantiser runs as its own pass, then
     csrc/gemm_tn_fp8_block_pipe.hip; no host sync, every tensor from the
-    caching allocator."""
-    if _use_hip(x):
+    caching allocator. x may also be the already-quantised pair (x_q [T, K],
+    x_s [K/128, T]) of `rmsnorm_quant_fp8`: the quantiser pass is skipped and
+    the result is bf16 (on CPU: `out_dtype`)."""
+    if _is_cuda_act(x):
         C = _require_hip()
         # fresh caching-allocator tensors: safe under hipGraph capture
-        x_q, x_s = C.quant_rows_fp8_block128(x.contiguous())
+        x_q, x_s = (x if isinstance(x, tuple)
+                    else C.quant_rows_fp8_block128(x.contiguous()))
         return C.gemm_fp8_block_pipelined(x_q, x_s, w_q, w_s, residual)
-    return torch_ref.linear_fp8_block128(x, w_q, w_s, residual)
+    return torch_ref.linear_fp8_block128(x, w_q, w_s, residual, out_dtype)
 
 
-def gate_up_silu_fp8_block128(x, w_q, w_s):
+def gate_up_silu_fp8_block128(x, w_q, w_s, out_dtype=None):
     """SwiGLU of the merged block-scaled gate_up projection (w_q [2I, K], gate
     rows first, w_s [2I/128, K/128]): one kernel, f32 SwiGLU on the unrounded
-    products, one rounding. Arithmetic: torch_ref.gate_up_silu_fp8_block128."""
-    if _use_hip(x):
+    products, one rounding. Arithmetic: torch_ref.gate_up_silu_fp8_block128.
+    x: a tensor or an already-quantised pair, as in `linear_fp8_block128`."""
+    if _is_cuda_act(x):
         C = _require_hip()
         # fresh caching-allocator tensors: safe under hipGraph capture
-        x_q, x_s = C.quant_rows_fp8_block128(x.contiguous())
+        x_q, x_s = (x if isinstance(x, tuple)
+                    else C.quant_rows_fp8_block128(x.contiguous()))
         return C.gemm_fp8_block_gate_up_silu(x_q, x_s, w_q, w_s)
-    return torch_ref.gate_up_silu_fp8_block128(x, w_q, w_s)
+    return torch_ref.gate_up_silu_fp8_block128(x, w_q, w_s, out_dtype)
+
+
+def rmsnorm_quant_fp8_supported(c: int, mode: str) -> bool:
+    """Row widths csrc/rmsnorm_quant_fp8.hip takes: up to 16384 elements in
+    16-byte chunks for "rows", whole 128-element groups for "block128"."""
+    return 8 <= c <= 16384 and c % (128 if mode == "block128" else 8) == 0
+
+
+def rmsnorm_quant_fp8(x, residual, weight, eps: float, mode: str):
+    """The norm in front of a dense FP8 projection with that projection's
+    activation quantiser fused in: (residual += x when a residual is given,)
+    normalise, round to bf16 in registers, quantise. mode "rows": codes
+    [T, Kp] + scales [T] (`linear_fp8`, `gate_up_silu_fp8`); mode "block128":
+    codes [T, K] + scales [K/128, T] (the `_block128` pair). Returns (x_q,
+    x_s, residual), residual being x itself when none was given. One kernel
+    (csrc/rmsnorm_quant_fp8.hip) on GPU, no bf16 normalised rows in memory,
+    bit-equal to `fused_add_rmsnorm` / `rmsnorm` followed by the quantiser —
+    which is the CPU path: torch_ref.rmsnorm_quant_fp8."""
+    if _use_hip(x):
+        if mode not in ("rows", "block128"):
+            raise ValueError(
+                f"mode must be 'rows' or 'block128', got {mode!r}")
+        x_q, x_s = _require_hip().rmsnorm_quant_fp8(
+            x, residual, weight, eps, 1 if mode == "block128" else 0)
+        return x_q, x_s, x if residual is None else residual
+    return torch_ref.rmsnorm_quant_fp8(x, residual, weight, eps, mode)
 
 
 def grouped_gemm_fp8_block128_qualifies(n: int, k: int) -> bool:

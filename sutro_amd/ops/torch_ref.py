@@ -318,7 +318,17 @@ def quantize_act_fp8(x, quantize_rows=None):
     return (quantize_rows or quantize_rows_fp8)(x.contiguous(), x_q, x_s)
 
 
-def linear_fp8(x, w_q, w_scale, residual=None):
+def _act_pair(x, quantize, out_dtype=None):
+    """(codes, scales, result dtype) of a projection's activation: x is a
+    tensor, quantised here by `quantize`, or an already-quantised pair
+    (x_q, x_s) as `rmsnorm_quant_fp8` returns it, whose projection result
+    is `out_dtype` (default bf16, what the GPU kernels write)."""
+    if isinstance(x, tuple):
+        return x[0], x[1], out_dtype or torch.bfloat16
+    return (*quantize(x), x.dtype)
+
+
+def linear_fp8(x, w_q, w_scale, residual=None, out_dtype=None):
     """THE statement of the dense W8A8 projection (csrc/gemm_tn_fp8_pipe.hip):
     x [T, K] -> out [T, N] in x's dtype, for w_q [N, Kp] e4m3 + w_scale [N]
     f32 (one scale per output channel, `quantize_weight_fp8` of the local
@@ -328,14 +338,14 @@ def linear_fp8(x, w_q, w_scale, residual=None):
         y        = fp8_linear(x_q, x_s, w_q, w_scale)   (f32)
         y        = y + f32(residual)                  (when given)
         out      = y rounded once to x's dtype"""
-    x_q, x_s = quantize_act_fp8(x)
+    x_q, x_s, dtype = _act_pair(x, quantize_act_fp8, out_dtype)
     y = fp8_linear(x_q, x_s, w_q, w_scale)
     if residual is not None:
         y = y + residual.float()
-    return y.to(x.dtype)
+    return y.to(dtype)
 
 
-def gate_up_silu_fp8(x, w_q, w_scale):
+def gate_up_silu_fp8(x, w_q, w_scale, out_dtype=None):
     """SwiGLU of the merged W8A8 gate_up projection: w_q [2I, Kp] (gate rows
     first) + w_scale [2I]; returns [T, I] in x's dtype.
 
@@ -344,10 +354,10 @@ def gate_up_silu_fp8(x, w_q, w_scale):
 
     Unlike the bf16 gate_up path, the two products are NOT rounded before the
     activation (the grouped FP8 kernel's epilogue)."""
-    x_q, x_s = quantize_act_fp8(x)
+    x_q, x_s, dtype = _act_pair(x, quantize_act_fp8, out_dtype)
     y = fp8_linear(x_q, x_s, w_q, w_scale)
     inter = w_q.shape[0] // 2
-    return (torch.nn.functional.silu(y[:, :inter]) * y[:, inter:]).to(x.dtype)
+    return (torch.nn.functional.silu(y[:, :inter]) * y[:, inter:]).to(dtype)
 
 
 FP8_BLOCK = 128
@@ -425,7 +435,7 @@ def fp8_block_linear(a_q, a_s, w_q, w_s):
     return acc
 
 
-def linear_fp8_block128(x, w_q, w_s, residual=None):
+def linear_fp8_block128(x, w_q, w_s, residual=None, out_dtype=None):
     """THE statement of the block-scaled dense projection
     (csrc/gemm_tn_fp8_block_pipe.hip): x [T, K] -> out [T, N] in x's dtype,
     for w_q [N, K] e4m3 + w_s [N/128, K/128] f32 (`weight`,
@@ -435,14 +445,14 @@ def linear_fp8_block128(x, w_q, w_s, residual=None):
         y        = fp8_block_linear(x_q, x_s, w_q, w_s)   (f32)
         y        = y + f32(residual)                  (when given)
         out      = y rounded once to x's dtype"""
-    x_q, x_s = quantize_rows_fp8_block128(x)
+    x_q, x_s, dtype = _act_pair(x, quantize_rows_fp8_block128, out_dtype)
     y = fp8_block_linear(x_q, x_s, w_q, w_s)
     if residual is not None:
         y = y + residual.float()
-    return y.to(x.dtype)
+    return y.to(dtype)
 
 
-def gate_up_silu_fp8_block128(x, w_q, w_s):
+def gate_up_silu_fp8_block128(x, w_q, w_s, out_dtype=None):
     """SwiGLU of the merged block-scaled gate_up projection: w_q [2I, K]
     (gate rows first) + w_s [2I/128, K/128], I % 128 == 0; returns [T, I] in
     x's dtype.
@@ -452,10 +462,31 @@ def gate_up_silu_fp8_block128(x, w_q, w_s):
 
     As in `gate_up_silu_fp8`, the two products are not rounded before the
     activation."""
-    x_q, x_s = quantize_rows_fp8_block128(x)
+    x_q, x_s, dtype = _act_pair(x, quantize_rows_fp8_block128, out_dtype)
     y = fp8_block_linear(x_q, x_s, w_q, w_s)
     inter = w_q.shape[0] // 2
-    return (torch.nn.functional.silu(y[:, :inter]) * y[:, inter:]).to(x.dtype)
+    return (torch.nn.functional.silu(y[:, :inter]) * y[:, inter:]).to(dtype)
+
+
+def rmsnorm_quant_fp8(x, residual, weight, eps: float, mode: str):
+    """THE statement of the fused norm + activation quantiser
+    (csrc/rmsnorm_quant_fp8.hip), the composition it replaces:
+
+        y, residual = fused_add_rmsnorm(x, residual)   (rmsnorm(x) and
+                                                        residual = x when
+                                                        residual is None)
+        x_q, x_s    = quantize_act_fp8(y)              mode "rows"
+                      quantize_rows_fp8_block128(y)    mode "block128"
+
+    Returns (x_q, x_s, residual)."""
+    if mode not in ("rows", "block128"):
+        raise ValueError(f"mode must be 'rows' or 'block128', got {mode!r}")
+    if residual is None:
+        y, residual = rmsnorm(x, weight, eps), x
+    else:
+        y, residual = fused_add_rmsnorm(x, residual, weight, eps)
+    quantize = quantize_act_fp8 if mode == "rows" else quantize_rows_fp8_block128
+    return (*quantize(y), residual)
 
 
 def grouped_gemm_fp8(out, a_q, a_scale, w_q, w_scale, row_tok, tile_off,

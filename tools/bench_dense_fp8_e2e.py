@@ -3,6 +3,9 @@ for it, so this builds the engine directly with each of its values ("bf16",
 "fp8_e4m3", "fp8_block128"), at
 bench.py's default operating point (Qwen3-32B, 2048 rows, prompt 128, 128 new
 tokens), and reports ms per decode step and resident KV blocks for each.
+`--dense-act-quant fused` (or `both`) also runs the FP8 settings with the
+activation quantiser fused into the norms (EngineConfig.dense_act_quant);
+`--dense` limits the run to some settings.
 
 Per setting: a fresh engine kept saturated the way bench.py keeps it (rows
 of `--prompt-len` random tokens, finished rows — random weights do sample
@@ -46,14 +49,14 @@ from sutro_amd.models.registry import (get_model_spec,  # noqa: E402
 SETTINGS = ("bf16", "fp8_e4m3", "fp8_block128")
 
 
-def run(args, dense, gpu):
+def run(args, dense, gpu, act_quant="separate"):
     cfg = EngineConfig(
         spec=get_model_spec(args.model) if gpu else tiny_spec_for_tests(),
         device="cuda" if gpu else "cpu",
         max_model_len=max(256, args.prompt_len + args.max_new + 32),
         max_num_seqs=args.batch, max_tokens_per_step=args.tokens_per_step,
         seed=0, num_kv_blocks=None if gpu else 512,
-        dense_weight_dtype=dense)
+        dense_weight_dtype=dense, dense_act_quant=act_quant)
 
     def sync():
         if gpu:
@@ -116,7 +119,7 @@ def run(args, dense, gpu):
     if len(ms) * 2 < args.steps:
         raise RuntimeError(f"only {len(ms)} of {args.steps} timed steps were "
                            "pure decode")
-    out = dict(dense_weight_dtype=dense,
+    out = dict(dense_weight_dtype=dense, dense_act_quant=act_quant,
                ms_per_decode_step=statistics.median(ms), ms_min=min(ms),
                ms_max=max(ms), decode_steps=len(ms), mixed_steps=mixed,
                rows_min=min(rows), rows_max=max(rows),
@@ -141,23 +144,39 @@ def main():
                          "result as a JSON line (what the tool starts, one "
                          "fresh process per setting, so that the memory "
                          "figures of one do not depend on the other)")
+    ap.add_argument("--dense", default=None, metavar="DTYPE,..",
+                    help="run only these dense_weight_dtype settings")
+    ap.add_argument("--dense-act-quant", default="separate",
+                    choices=["separate", "fused", "both"],
+                    help="dense_act_quant of the FP8 settings (bf16 has no "
+                         "quantiser and runs once)")
+    ap.add_argument("--only-act-quant", default="separate",
+                    choices=["separate", "fused"],
+                    help="with --only: that process's dense_act_quant")
     args = ap.parse_args()
     gpu = torch.cuda.is_available()
     if not gpu:
         args.batch = min(args.batch, 32)
         args.prompt_len = min(args.prompt_len, 16)
         args.tokens_per_step = min(args.tokens_per_step, 128)
-    cols = ["dense_weight_dtype", "ms_per_decode_step", "ms_min", "ms_max",
+    cols = ["dense_weight_dtype", "dense_act_quant", "ms_per_decode_step", "ms_min", "ms_max",
             "decode_steps", "mixed_steps", "rows_min", "rows_max",
             "kv_blocks", "kv_blocks_fit", "engine_init_s",
             "free_after_init_gb", "allocated_after_init_gb", "graph"]
     if args.only:
-        print("RESULT " + json.dumps(run(args, args.only, gpu)), flush=True)
+        print("RESULT " + json.dumps(run(args, args.only, gpu,
+                                         args.only_act_quant)), flush=True)
         return
     lines = [",".join(cols)]
-    for dense in SETTINGS:
+    hows = (("separate", "fused") if args.dense_act_quant == "both"
+            else (args.dense_act_quant,))
+    runs = [(dense, how) for dense in SETTINGS
+            if not args.dense or dense in args.dense.split(",")
+            for how in (hows if dense != "bf16" else ("separate",))]
+    for dense, how in runs:
         r = None
-        with subprocess.Popen([sys.executable, __file__, "--only", dense]
+        with subprocess.Popen([sys.executable, __file__, "--only", dense,
+                               "--only-act-quant", how]
                               + sys.argv[1:], stdout=subprocess.PIPE,
                               text=True) as child:
             for line in child.stdout:
@@ -166,7 +185,7 @@ def main():
                 else:
                     print(line, end="", flush=True)
         if child.returncode != 0 or r is None:
-            raise SystemExit(f"the {dense} run failed "
+            raise SystemExit(f"the {dense} / {how} run failed "
                              f"(exit {child.returncode}); stopping")
         print(r, flush=True)
         lines.append(",".join(f"{r[c]:.2f}" if isinstance(r[c], float)
